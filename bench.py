@@ -12,6 +12,15 @@ Launch (driver contract):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 
+A plain run does only what the headline figure needs: set up, warm up,
+time the K saves, print the result line. ``--full`` adds the secondary
+measurements (async_take stall, restore throughput), each of which takes
+runs of its own. ``--dump-outputs DIR`` writes what the last timed save
+put on disk, read back through Snapshot.read_object, as DIR/<name>.npy
+(float32; tensors too large for the dump budget are stored as a fixed,
+seeded sample of their elements). The synthetic state is seeded, so two
+runs with the same arguments save identical values.
+
 At every N (including 1) each rank holds 1/N of every parameter as a
 DTensor on a 1-D mesh (FSDP2-style layout), so the FSDP write path named
 by the metric is always the one timed; if the 1-rank process group can't
@@ -33,6 +42,47 @@ import torch
 # save to local FS on p4d.24xlarge (1 GPU ~13.91 s, 8 GPUs
 # ~3.38 s). 2/4-GPU points interpolated geometrically.
 _BASELINE_GBPS = {1: 1.44, 2: 2.29, 4: 3.65, 8: 5.92}
+
+_STATE_SEED = 20240531  # synthetic model state
+_DUMP_SEED = 977  # element sample of --dump-outputs
+# --dump-outputs writes at most this much (float32) across all tensors
+_DUMP_BUDGET_BYTES = 48 * 1024 * 1024
+
+
+def _default_bench_dir() -> str:
+    """/tmp/tsamd_bench, or a per-user sibling when another user owns it."""
+    path = "/tmp/tsamd_bench"
+    if os.path.exists(path) and not os.access(path, os.W_OK | os.X_OK):
+        path = f"{path}_{os.getuid()}"
+    return path
+
+
+def dump_outputs(ckpt_path: str, names: List[str], out_dir: str) -> None:
+    """Write what the snapshot at ``ckpt_path`` stores for each tensor of
+    the "model" state as ``out_dir/<name>.npy`` (float32).
+
+    Every tensor is read back from storage in full (sharded ones are
+    reassembled). Each gets an equal share of the dump budget; one that
+    fits is written whole, a larger one as the elements at a sorted index
+    sample drawn from a fixed seed, so two runs pick the same elements."""
+    import numpy as np
+
+    from torchsnapshot_amd import Snapshot
+
+    os.makedirs(out_dir, exist_ok=True)
+    snap = Snapshot(ckpt_path)
+    cap = max(1, _DUMP_BUDGET_BYTES // 4 // max(1, len(names)))
+    gen = torch.Generator().manual_seed(_DUMP_SEED)
+    for name in names:
+        t = snap.read_object(f"0/model/{name}")
+        flat = t.detach().cpu().reshape(-1)
+        if flat.numel() > cap:
+            idx = torch.randint(flat.numel(), (cap,), generator=gen)
+            flat = flat[idx.sort().values]
+        np.save(
+            os.path.join(out_dir, f"{name}.npy"),
+            flat.to(torch.float32).numpy(),
+        )
 
 
 def tiny_shapes() -> List[Tuple[str, Tuple[int, ...]]]:
@@ -152,7 +202,21 @@ def main() -> None:
     parser.add_argument(
         "--model", choices=["llama3-8b", "tiny"], default="llama3-8b"
     )
+    parser.add_argument(
+        "--full",
+        action="store_true",
+        help="also measure the async_take stall and restore throughput",
+    )
+    parser.add_argument(
+        "--dump-outputs",
+        type=str,
+        default="",
+        metavar="DIR",
+        help="write what the last timed save stored as DIR/<name>.npy",
+    )
     args = parser.parse_args()
+    if args.steps < 1:
+        parser.error("--steps must be at least 1")
 
     from torchsnapshot_amd import Snapshot
 
@@ -209,13 +273,16 @@ def main() -> None:
         except Exception:
             use_dtensor = False
 
-    bench_dir = args.dir or "/tmp/tsamd_bench"
+    bench_dir = args.dir or _default_bench_dir()
     ckpt_path = os.path.join(bench_dir, "ckpt")
     if rank == 0:
         os.makedirs(bench_dir, exist_ok=True)
         shutil.rmtree(ckpt_path, ignore_errors=True)
     _barrier(world_size)
 
+    # same arguments -> same synthetic state, run after run (per-rank
+    # offset so shards differ across ranks)
+    torch.manual_seed(_STATE_SEED + rank)
     state, total_bytes = build_state(
         device,
         world_size,
@@ -248,26 +315,37 @@ def main() -> None:
     ms_per_step = elapsed / args.steps * 1000.0
     gbps = (total_bytes / 1e9) / (elapsed / args.steps)
 
-    # async_take stall: how long the "training thread" is blocked.
-    # Drain the timed loop's writeback backlog first (untimed) so the
-    # stall reflects the snapshot machinery, not 16 GB/step of dirty
-    # pages flushing under the measurement's CPU.
-    os.sync()
-    _barrier(world_size)
-    t0 = time.monotonic()
-    pending = Snapshot.async_take(ckpt_path, app_state)
-    stall_s = time.monotonic() - t0
-    pending.wait()
-    stall_s = _max_over_ranks(stall_s, world_size, device)
+    if args.dump_outputs:
+        if rank == 0:
+            dump_outputs(ckpt_path, list(state.state_dict()), args.dump_outputs)
+        _barrier(world_size)
 
-    # informational: one restore of the full state (untimed region for the
-    # headline metric; reported as restore_GBps)
-    _barrier(world_size)
-    t0 = time.monotonic()
-    Snapshot(ckpt_path).restore({"model": state})
-    restore_s = _max_over_ranks(
-        time.monotonic() - t0, world_size, device
-    )
+    extras: Dict[str, float] = {}
+    if args.full:
+        # async_take stall: how long the "training thread" is blocked.
+        # Drain the timed loop's writeback backlog first (untimed) so the
+        # stall reflects the snapshot machinery, not 16 GB/step of dirty
+        # pages flushing under the measurement's CPU.
+        os.sync()
+        _barrier(world_size)
+        t0 = time.monotonic()
+        pending = Snapshot.async_take(ckpt_path, app_state)
+        stall_s = time.monotonic() - t0
+        pending.wait()
+        stall_s = _max_over_ranks(stall_s, world_size, device)
+
+        # informational: one restore of the full state (reported as
+        # restore_GBps)
+        _barrier(world_size)
+        t0 = time.monotonic()
+        Snapshot(ckpt_path).restore({"model": state})
+        restore_s = _max_over_ranks(
+            time.monotonic() - t0, world_size, device
+        )
+        extras = {
+            "stall_sec": round(stall_s, 3),
+            "restore_GBps": round((total_bytes / 1e9) / restore_s, 3),
+        }
 
     if rank == 0 and not args.keep:
         shutil.rmtree(ckpt_path, ignore_errors=True)
@@ -287,8 +365,7 @@ def main() -> None:
             "vs_baseline": round(gbps / baseline, 3) if baseline else None,
             "dtype": "bf16",
             "data": "synthetic",
-            "stall_sec": round(stall_s, 3),
-            "restore_GBps": round((total_bytes / 1e9) / restore_s, 3),
+            **extras,
             "config": {
                 "model": "llama-3-8b" if args.model != "tiny" else "tiny",
                 "model_bytes": total_bytes,
