@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import asyncio
 from collections import defaultdict
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -74,7 +74,7 @@ def batch_write_requests(
         cur: List[WriteReq] = []
         cur_bytes = 0
         for req in members:
-            nbytes = req.stager.tensor.numel() * req.stager.tensor.element_size()
+            nbytes = req.stager.stored_nbytes()
             aligned = (nbytes + ALIGN - 1) // ALIGN * ALIGN
             if cur and cur_bytes + aligned > slab_limit:
                 out.append(_make_slab(device_str, cur, rank, seq))
@@ -95,15 +95,21 @@ def _make_slab(
 ) -> WriteReq:
     slab_path = f"batched/{rank}-{seq}"
     tensors = [m.stager.tensor.detach() for m in members]
-    _, offsets, total = build_pack_items(tensors)
+    # stored dtype per member (None = as is): a slab mixing cast and
+    # uncast members is still one gather launch, laid out in stored bytes
+    out_dtypes = [m.stager.save_dtype for m in members]
+    _, offsets, total = build_pack_items(tensors, out_dtypes)
     for m, off in zip(members, offsets):
         entry = m.tensor_entry
-        nbytes = m.stager.tensor.numel() * m.stager.tensor.element_size()
+        nbytes = m.stager.stored_nbytes()
         entry.location = slab_path
         entry.byte_range = [off, off + nbytes]
     is_async = any(m.stager.is_async_snapshot for m in members)
     stager = BatchedBufferStager(
-        tensors=tensors, total_bytes=total, is_async_snapshot=is_async
+        tensors=tensors,
+        total_bytes=total,
+        is_async_snapshot=is_async,
+        out_dtypes=out_dtypes,
     )
     return WriteReq(path=slab_path, stager=stager)
 
@@ -114,8 +120,12 @@ class BatchedBufferStager(BufferStager):
         tensors: Sequence[torch.Tensor],
         total_bytes: int,
         is_async_snapshot: bool,
+        out_dtypes: Optional[Sequence[Optional[torch.dtype]]] = None,
     ) -> None:
         self.tensors = tensors
+        self.out_dtypes = (
+            list(out_dtypes) if out_dtypes is not None else [None] * len(tensors)
+        )
         self.total_bytes = total_bytes
         self.is_async_snapshot = is_async_snapshot
         self._staged_batch = None
@@ -140,7 +150,9 @@ class BatchedBufferStager(BufferStager):
 
         engine = get_staging_engine(self.tensors[0].device)
         ck = integrity.checksumming_enabled()
-        batch = engine.stage(self.tensors, compute_checksums=ck)
+        batch = engine.stage(
+            self.tensors, compute_checksums=ck, out_dtypes=self.out_dtypes
+        )
         batch.wait()
         if ck and batch.checksums is not None:
             # padding is zeroed, so the slab-file checksum is the sum of
@@ -159,14 +171,16 @@ class BatchedBufferStager(BufferStager):
     def _stage_cpu(self) -> BufferType:
         from . import integrity
 
-        items, offsets, total = build_pack_items(self.tensors)
+        items, offsets, total = build_pack_items(self.tensors, self.out_dtypes)
         slab = bytearray(total)
         mv = memoryview(slab)
         from .serialization import tensor_as_memoryview
 
         ck = integrity.checksumming_enabled()
         members = []
-        for t, off in zip(self.tensors, offsets):
+        for t, off, out_dtype in zip(self.tensors, offsets, self.out_dtypes):
+            if out_dtype is not None and out_dtype != t.dtype:
+                t = t.to(out_dtype)
             nbytes = t.numel() * t.element_size()
             if nbytes == 0:
                 continue
@@ -193,6 +207,7 @@ class BatchedBufferStager(BufferStager):
             self._staged_batch.release()
             self._staged_batch = None
         self.tensors = ()  # free shadow clones as soon as the write lands
+        self.out_dtypes = []
 
 
 # ---------------------------------------------------------------------------

@@ -71,8 +71,11 @@ def prepare_write(
     rank: int,
     replicated: bool = False,
     is_async_snapshot: bool = False,
+    save_dtype: Optional[torch.dtype] = None,
 ) -> Tuple[Entry, List[WriteReq]]:
     """Build the manifest entry + write requests for one flattened leaf.
+    ``save_dtype`` (tensor leaves only) stores the leaf narrowed to that
+    dtype; the caller decides which leaves qualify.
 
     No data moves here — stagers capture references; the scheduler drives
     the actual staging and storage I/O later."""
@@ -85,13 +88,19 @@ def prepare_write(
         from .io_preparers.sharded_tensor import ShardedTensorIOPreparer
 
         return ShardedTensorIOPreparer.prepare_write(
-            storage_path, obj, is_async_snapshot=is_async_snapshot
+            storage_path,
+            obj,
+            is_async_snapshot=is_async_snapshot,
+            save_dtype=save_dtype,
         )
     if _is_dtensor(obj):
         from .io_preparers.dtensor import DTensorIOPreparer
 
         return DTensorIOPreparer.prepare_write(
-            storage_path, obj, is_async_snapshot=is_async_snapshot
+            storage_path,
+            obj,
+            is_async_snapshot=is_async_snapshot,
+            save_dtype=save_dtype,
         )
     if isinstance(obj, torch.Tensor):
         if should_chunk(obj):
@@ -100,12 +109,14 @@ def prepare_write(
                 obj,
                 replicated=replicated,
                 is_async_snapshot=is_async_snapshot,
+                save_dtype=save_dtype,
             )
         return TensorIOPreparer.prepare_write(
             storage_path,
             obj,
             replicated=replicated,
             is_async_snapshot=is_async_snapshot,
+            save_dtype=save_dtype,
         )
     return ObjectIOPreparer.prepare_write(storage_path, obj, replicated=replicated)
 

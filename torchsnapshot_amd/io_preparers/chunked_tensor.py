@@ -52,7 +52,10 @@ class ChunkedTensorIOPreparer:
         tensor: torch.Tensor,
         replicated: bool = False,
         is_async_snapshot: bool = False,
+        save_dtype: Optional[torch.dtype] = None,
     ) -> Tuple[ChunkedTensorEntry, List[WriteReq]]:
+        # chunk planning stays in source bytes; entries record the stored
+        # dtype
         plan = _chunk_plan(list(tensor.shape), tensor.element_size())
         chunks: List[Shard] = []
         write_reqs: List[WriteReq] = []
@@ -65,6 +68,7 @@ class ChunkedTensorIOPreparer:
                 tensor=chunk,
                 replicated=replicated,
                 is_async_snapshot=is_async_snapshot,
+                save_dtype=save_dtype,
             )
             chunks.append(
                 Shard(
@@ -75,7 +79,7 @@ class ChunkedTensorIOPreparer:
             )
             write_reqs.extend(sub_reqs)
         entry = ChunkedTensorEntry(
-            dtype=dtype_to_str(tensor.dtype),
+            dtype=dtype_to_str(save_dtype or tensor.dtype),
             shape=list(tensor.shape),
             chunks=chunks,
             replicated=replicated,

@@ -115,6 +115,7 @@ class DTensorIOPreparer:
         storage_path: str,
         obj: Any,  # DTensor
         is_async_snapshot: bool = False,
+        save_dtype: Optional[torch.dtype] = None,
     ) -> Tuple[DTensorEntry, List[WriteReq]]:
         local = obj.to_local()
         local_shape, global_offset = _local_global_offset(obj)
@@ -150,6 +151,7 @@ class DTensorIOPreparer:
                 tensor=piece,
                 replicated=False,
                 is_async_snapshot=is_async_snapshot,
+                save_dtype=save_dtype,
             )
             shards_meta.append(
                 ShardMeta(
@@ -163,7 +165,7 @@ class DTensorIOPreparer:
             shards=shards_meta,
             mesh=obj.device_mesh.mesh.tolist(),
             dim_map=_dim_map(obj),
-            dtype=dtype_to_str(obj.dtype),
+            dtype=dtype_to_str(save_dtype or obj.dtype),
             shape=list(obj.shape),
         )
         return entry, write_reqs

@@ -287,6 +287,7 @@ class ShardedTensorIOPreparer:
         storage_path: str,
         obj: Any,  # ShardedTensor
         is_async_snapshot: bool = False,
+        save_dtype: Optional[torch.dtype] = None,
     ) -> Tuple[ShardedTensorEntry, List[WriteReq]]:
         max_bytes = knobs.get_max_shard_size_bytes()
         shards_meta: List[ShardMeta] = []
@@ -304,6 +305,7 @@ class ShardedTensorIOPreparer:
                     tensor=piece,
                     replicated=False,
                     is_async_snapshot=is_async_snapshot,
+                    save_dtype=save_dtype,
                 )
                 shards_meta.append(
                     ShardMeta(
@@ -315,7 +317,7 @@ class ShardedTensorIOPreparer:
                 write_reqs.extend(sub_reqs)
         entry = ShardedTensorEntry(
             shards=shards_meta,
-            dtype=dtype_to_str(obj.dtype),
+            dtype=dtype_to_str(save_dtype or obj.dtype),
             shape=global_shape,
         )
         return entry, write_reqs

@@ -82,12 +82,23 @@ class TensorIOPreparer:
         tensor: torch.Tensor,
         replicated: bool = False,
         is_async_snapshot: bool = False,
+        save_dtype: Optional[torch.dtype] = None,
     ) -> Tuple[TensorEntry, List[WriteReq]]:
+        """``save_dtype`` stores the tensor narrowed to that dtype (the
+        entry records the STORED dtype); it requires the plain buffer
+        serializer."""
         serializer = pick_serializer(tensor)
+        if save_dtype == tensor.dtype:
+            save_dtype = None
+        if save_dtype is not None and serializer != SERIALIZER_BUFFER:
+            raise ValueError(
+                f"save_dtype={save_dtype} needs a buffer-serialized tensor, "
+                f"got serializer '{serializer}' for dtype {tensor.dtype}"
+            )
         entry = TensorEntry(
             location=storage_path,
             serializer=serializer,
-            dtype=dtype_to_str(tensor.dtype),
+            dtype=dtype_to_str(save_dtype or tensor.dtype),
             shape=list(tensor.shape),
             replicated=replicated,
         )
@@ -95,6 +106,7 @@ class TensorIOPreparer:
             tensor=tensor,
             serializer=serializer,
             is_async_snapshot=is_async_snapshot,
+            save_dtype=save_dtype,
         )
         return entry, [
             WriteReq(path=storage_path, stager=stager, tensor_entry=entry)
@@ -262,16 +274,30 @@ class TensorBufferStager(BufferStager):
         tensor: torch.Tensor,
         serializer: str,
         is_async_snapshot: bool = False,
+        save_dtype: Optional[torch.dtype] = None,
     ) -> None:
         self.tensor = tensor
         self.serializer = serializer
         self.is_async_snapshot = is_async_snapshot
+        # stored dtype when it differs from the tensor's (narrowing save):
+        # device tensors are cast inside the gather kernel, host tensors
+        # with torch in _stage_cpu
+        self.save_dtype = save_dtype
         self._staged_batch = None  # StagedBatch for device tensors
         # device staging computes this for free when TSAMD_CHECKSUM=1
         self.precomputed_checksum = None
 
+    def stored_nbytes(self) -> int:
+        """Payload bytes as written (after the save_dtype cast, if any)."""
+        esz = (
+            self.save_dtype.itemsize
+            if self.save_dtype is not None
+            else self.tensor.element_size()
+        )
+        return self.tensor.numel() * esz
+
     def get_staging_cost_bytes(self) -> int:
-        nbytes = self.tensor.numel() * self.tensor.element_size()
+        nbytes = self.stored_nbytes()
         if self.serializer in (SERIALIZER_TORCH_SAVE, SERIALIZER_QTENSOR):
             # these serializers materialize a second copy while packing
             return 2 * nbytes
@@ -298,6 +324,11 @@ class TensorBufferStager(BufferStager):
             # managed memory is CPU-addressable: serialize zero-copy, no
             # D2H needed (clone when async: training may mutate the pages)
             cpu = uvm_to_cpu(t)
+            if self.save_dtype is not None:
+                # the cast result is already a private copy
+                return tensor_as_memoryview(
+                    cpu.to(self.save_dtype).contiguous()
+                )
             if self.is_async_snapshot:
                 cpu = cpu.clone()
             return tensor_as_memoryview(cpu.contiguous())
@@ -305,7 +336,11 @@ class TensorBufferStager(BufferStager):
 
         engine = get_staging_engine(t.device)
         ck = integrity.checksumming_enabled()
-        batch = engine.stage([t], compute_checksums=ck)
+        batch = engine.stage(
+            [t],
+            compute_checksums=ck,
+            out_dtypes=None if self.save_dtype is None else [self.save_dtype],
+        )
         batch.wait()  # blocks in executor thread; GIL released inside HIP
         if ck and batch.checksums is not None:
             self.precomputed_checksum = "psum64:" + format(
@@ -320,6 +355,10 @@ class TensorBufferStager(BufferStager):
             return qtensor_as_bytes(t)
         if self.serializer == SERIALIZER_TORCH_SAVE:
             return torch_save_as_bytes(t)
+        if self.save_dtype is not None:
+            # runs on the executor thread; the cast result is a private
+            # copy, so async snapshots need no extra clone
+            return tensor_as_memoryview(t.to(self.save_dtype).contiguous())
         if self._should_copy_cpu_tensor(t, ctx):
             t = t.contiguous().clone() if not t.is_contiguous() else t.clone()
         elif not t.is_contiguous():

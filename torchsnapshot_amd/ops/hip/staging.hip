@@ -7,6 +7,8 @@
 //     in a single launch (replaces the reference's per-tensor
 //     UntypedStorage copies + ByteTensor slab, torchsnapshot/batcher.py
 //     :104-162, and its tensor.cpu() staging, io_preparers/tensor.py:353)
+//   - gather-and-cast: per-descriptor f32 -> bf16/f16 narrowing fused into
+//     the same launch (save_dtype), so only stored-size bytes leave the GPU
 //   - scatter kernel (same code path, direction-reversed) for restore
 //   - SDMA copies (hipMemcpyAsync) slab <-> pinned host memory; the slab
 //     can also be skipped entirely ("direct" mode): the kernel writes
@@ -66,7 +68,16 @@ struct Desc {
   uint32_t ndim;                 // number of outer (strided) dims
   uint32_t sizes[kMaxDims];
   long long strides[kMaxDims];   // byte strides of outer dims
+  // narrowing cast fused into the gather: 0 none, 1 f32->bf16, 2 f32->f16.
+  // With a cast, every flat-side quantity above (nbytes, row_bytes,
+  // flat_off, vec) is in DESTINATION bytes; tensor_base and strides stay
+  // in source bytes. A lane writes `vec` bytes and reads 2*vec.
+  uint32_t cast;
 };
+
+constexpr uint32_t kCastNone = 0;
+constexpr uint32_t kCastBF16 = 1;
+constexpr uint32_t kCastF16 = 2;
 
 // ---------------------------------------------------------------------------
 // psum64 checksum: an order-independent weighted word sum over the flat
@@ -204,7 +215,162 @@ __device__ unsigned long long process_range(const Desc& d, char* flat_base,
   return h;
 }
 
-template <bool GATHER, bool HASH>
+// ---------------------------------------------------------------------------
+// gather-and-cast (f32 -> bf16 / f16). Integer round-to-nearest-even on
+// the bit patterns: no dependence on the wave's denormal mode, so f32
+// subnormal inputs and f16 subnormal results are exact. The kernel is
+// PCIe- or HBM-bound; the handful of integer ops per element is free.
+// ---------------------------------------------------------------------------
+
+__device__ __host__ inline uint32_t f32_to_bf16_bits(uint32_t u) {
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) {
+    return (u >> 16) | 0x0040u;  // NaN stays NaN (quiet bit set)
+  }
+  // RNE; the carry runs into the exponent, so overflow lands on +-inf
+  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+__device__ __host__ inline uint32_t f32_to_f16_bits(uint32_t u) {
+  const uint32_t sign = (u >> 16) & 0x8000u;
+  const uint32_t a = u & 0x7FFFFFFFu;
+  if (a > 0x7F800000u) return sign | 0x7E00u;   // NaN
+  if (a >= 0x47800000u) return sign | 0x7C00u;  // >= 65536 (and inf)
+  if (a >= 0x38800000u) {
+    // f16-normal range: rebias the exponent (127 -> 15), RNE off 13 bits;
+    // 65520 <= |x| < 65536 carries to 0x7C00 = inf
+    uint32_t r = a - 0x38000000u;
+    r += 0x0FFFu + ((r >> 13) & 1u);
+    return sign | (r >> 13);
+  }
+  if (a < 0x33000000u) return sign;  // < 2^-25 (incl. f32 subnormals): +-0
+  // f16-subnormal range: result = RNE(|x| / 2^-24); shift is 14..24
+  const uint32_t mant = (a & 0x007FFFFFu) | 0x00800000u;
+  const uint32_t shift = 126u - (a >> 23);
+  uint32_t h = mant >> shift;
+  const uint32_t rem = mant & ((1u << shift) - 1u);
+  const uint32_t half = 1u << (shift - 1u);
+  if (rem > half || (rem == half && (h & 1u))) ++h;  // may carry to 0x0400
+  return sign | h;
+}
+
+__device__ inline uint32_t cast_pair(uint32_t lo, uint32_t hi, uint32_t code) {
+  // two f32 bit patterns -> two 16-bit results packed little-endian
+  if (code == kCastBF16) {
+    return (f32_to_bf16_bits(lo) & 0xFFFFu) | (f32_to_bf16_bits(hi) << 16);
+  }
+  return f32_to_f16_bits(lo) | (f32_to_f16_bits(hi) << 16);
+}
+
+// Convert 2*VEC source bytes at `src` into VEC bytes at `flat`. Every load
+// and store is naturally aligned to its own width (the host picks vec so).
+// When HASH, returns the psum64 contribution of the STORED bytes.
+template <int VEC, bool HASH>
+__device__ inline unsigned long long cast_vec(char* flat, const char* src,
+                                              uint32_t code,
+                                              unsigned long long file_off) {
+  unsigned long long h = 0;
+  if (VEC == 16) {
+    const uint4 a = *reinterpret_cast<const uint4*>(src);
+    const uint4 b = *reinterpret_cast<const uint4*>(src + 16);
+    uint4 o;
+    o.x = cast_pair(a.x, a.y, code);
+    o.y = cast_pair(a.z, a.w, code);
+    o.z = cast_pair(b.x, b.y, code);
+    o.w = cast_pair(b.z, b.w, code);
+    *reinterpret_cast<uint4*>(flat) = o;
+    if (HASH) {
+      unsigned long long w = file_off >> 3;
+      h += (((unsigned long long)o.y << 32) | o.x) * psum_mult(w);
+      h += (((unsigned long long)o.w << 32) | o.z) * psum_mult(w + 1);
+    }
+  } else if (VEC == 8) {
+    const uint4 a = *reinterpret_cast<const uint4*>(src);
+    uint2 o;
+    o.x = cast_pair(a.x, a.y, code);
+    o.y = cast_pair(a.z, a.w, code);
+    *reinterpret_cast<uint2*>(flat) = o;
+    if (HASH) {
+      h += (((unsigned long long)o.y << 32) | o.x) * psum_mult(file_off >> 3);
+    }
+  } else if (VEC == 4) {
+    const uint2 a = *reinterpret_cast<const uint2*>(src);
+    const uint32_t o = cast_pair(a.x, a.y, code);
+    *reinterpret_cast<uint32_t*>(flat) = o;
+    if (HASH) {
+      h += ((unsigned long long)o << (8 * (file_off & 7))) *
+           psum_mult(file_off >> 3);
+    }
+  } else {
+    const uint32_t a = *reinterpret_cast<const uint32_t*>(src);
+    const uint32_t o = (code == kCastBF16 ? f32_to_bf16_bits(a)
+                                          : f32_to_f16_bits(a)) & 0xFFFFu;
+    *reinterpret_cast<uint16_t*>(flat) = (uint16_t)o;
+    if (HASH) {
+      h += ((unsigned long long)o << (8 * (file_off & 7))) *
+           psum_mult(file_off >> 3);
+    }
+  }
+  return h;
+}
+
+// Cast counterpart of process_range: [s, e) and every index below are in
+// destination (flat-side) bytes; the source sits at twice the offset,
+// computed in 64 bits (a contiguous tensor just under 4 GiB stored has
+// just under 8 GiB of source).
+template <int VEC, bool HASH>
+__device__ unsigned long long process_range_cast(const Desc& d,
+                                                 char* flat_base, uint32_t s,
+                                                 uint32_t e) {
+  char* flat = flat_base + d.flat_off;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t rb = d.row_bytes;
+  const uint32_t code = d.cast;
+  unsigned long long h = 0;
+  if (d.ndim == 0 || rb == d.nbytes) {
+    const char* src = d.tensor_base;
+    for (uint32_t i = s + tid * VEC; i < e; i += kBlockThreads * VEC) {
+      h += cast_vec<VEC, HASH>(flat + i, src + 2ull * i, code, d.flat_off + i);
+    }
+    return h;
+  }
+  if (rb >= kWideRowBytes) {
+    // wide rows: rows sequential, lanes across columns
+    uint32_t row = s / rb;
+    uint32_t col = s - row * rb;
+    uint32_t off = s;
+    while (off < e) {
+      const char* src = d.tensor_base + row_offset(d, row) + 2ull * col;
+      uint32_t n = min(rb - col, e - off);
+      for (uint32_t i = tid * VEC; i < n; i += kBlockThreads * VEC) {
+        h += cast_vec<VEC, HASH>(flat + off + i, src + 2ull * i, code,
+                                 d.flat_off + off + i);
+      }
+      off += n;
+      ++row;
+      col = 0;
+    }
+  } else {
+    // narrow rows: one lane per row; flat-side writes stay coalesced
+    uint32_t first_row = s / rb;
+    uint32_t last_row = (e - 1) / rb;
+    for (uint32_t r = first_row + tid; r <= last_row; r += kBlockThreads) {
+      const char* src = d.tensor_base + row_offset(d, r);
+      uint32_t flat_pos = r * rb;
+      uint32_t lo = flat_pos < s ? (s - flat_pos) : 0;
+      uint32_t hi = (flat_pos + rb > e) ? (e - flat_pos) : rb;
+      for (uint32_t i = lo; i < hi; i += VEC) {
+        h += cast_vec<VEC, HASH>(flat + flat_pos + i, src + 2ull * i, code,
+                                 d.flat_off + flat_pos + i);
+      }
+    }
+  }
+  return h;
+}
+
+// CAST instantiations additionally route descriptors with a cast code to
+// process_range_cast; they are launched only for batches that contain one,
+// so uncast batches run exactly the kernels they always did.
+template <bool GATHER, bool HASH, bool CAST = false>
 __global__ __launch_bounds__(kBlockThreads) void pack_kernel(
     const Desc* __restrict__ descs, int n,
     const unsigned long long* __restrict__ wu_prefix,
@@ -224,12 +390,21 @@ __global__ __launch_bounds__(kBlockThreads) void pack_kernel(
     uint32_t e = s + kWorkUnitBytes > d.nbytes ? d.nbytes
                                                : s + kWorkUnitBytes;
     unsigned long long h = 0;
-    switch (d.vec) {
-      case 16: h = process_range<16, GATHER, HASH>(d, flat_base, s, e); break;
-      case 8: h = process_range<8, GATHER, HASH>(d, flat_base, s, e); break;
-      case 4: h = process_range<4, GATHER, HASH>(d, flat_base, s, e); break;
-      case 2: h = process_range<2, GATHER, HASH>(d, flat_base, s, e); break;
-      default: h = process_range<1, GATHER, HASH>(d, flat_base, s, e); break;
+    if (CAST && d.cast != kCastNone) {
+      switch (d.vec) {
+        case 16: h = process_range_cast<16, HASH>(d, flat_base, s, e); break;
+        case 8: h = process_range_cast<8, HASH>(d, flat_base, s, e); break;
+        case 4: h = process_range_cast<4, HASH>(d, flat_base, s, e); break;
+        default: h = process_range_cast<2, HASH>(d, flat_base, s, e); break;
+      }
+    } else {
+      switch (d.vec) {
+        case 16: h = process_range<16, GATHER, HASH>(d, flat_base, s, e); break;
+        case 8: h = process_range<8, GATHER, HASH>(d, flat_base, s, e); break;
+        case 4: h = process_range<4, GATHER, HASH>(d, flat_base, s, e); break;
+        case 2: h = process_range<2, GATHER, HASH>(d, flat_base, s, e); break;
+        default: h = process_range<1, GATHER, HASH>(d, flat_base, s, e); break;
+      }
     }
     if (HASH) {
       // wave64 reduction, then one atomic per wave per work unit
@@ -308,8 +483,8 @@ void chain_after(hipStream_t side, uintptr_t producer_stream, int device) {
   }
 }
 
-// flat desc rows from python: 18 u64 each (see ops/staging.py)
-constexpr int kRowInts = 18;
+// flat desc rows from python: 19 u64 each (see ops/staging.py)
+constexpr int kRowInts = 19;
 
 std::vector<Desc> parse_descs(const std::vector<unsigned long long>& flat,
                               int n) {
@@ -337,6 +512,31 @@ std::vector<Desc> parse_descs(const std::vector<unsigned long long>& flat,
     if (d.ndim > (uint32_t)kMaxDims) {
       throw std::runtime_error("too many outer dims");
     }
+    if (r[18] > kCastF16) {
+      throw std::runtime_error("unknown cast code in descriptor");
+    }
+    d.cast = (uint32_t)r[18];
+    if (d.cast != kCastNone && d.nbytes != 0) {
+      // the cast lanes do vector loads of 2*vec and stores of vec bytes:
+      // refuse a descriptor whose layout would misalign or overrun them
+      const uint32_t v = d.vec;
+      if (v != 16 && v != 8 && v != 4 && v != 2) {
+        throw std::runtime_error("cast descriptor: vec must be 16/8/4/2");
+      }
+      if (d.row_bytes == 0 || d.row_bytes % v != 0 ||
+          d.nbytes % d.row_bytes != 0) {
+        throw std::runtime_error("cast descriptor: row_bytes/vec mismatch");
+      }
+      const unsigned long long src_align = v == 16 ? 16 : 2ull * v;
+      bool ok = (r[0] % src_align) == 0;
+      for (uint32_t k = 0; k < d.ndim; ++k) {
+        ok = ok && ((unsigned long long)d.strides[k] % src_align) == 0;
+      }
+      if (!ok) {
+        throw std::runtime_error(
+            "cast descriptor: source not aligned for its vec");
+      }
+    }
   }
   return descs;
 }
@@ -350,6 +550,13 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
   hipStream_t stream = gather ? ctx.d2h_stream : ctx.h2d_stream;
 
   std::vector<Desc> descs = parse_descs(flat, n);
+  bool any_cast = false;
+  for (const Desc& d : descs) any_cast = any_cast || d.cast != kCastNone;
+  if (any_cast && !gather) {
+    // widening on restore stays with torch; refuse before touching the GPU
+    throw std::runtime_error(
+        "scatter_h2d does not support cast descriptors (gather only)");
+  }
   std::vector<unsigned long long> wu_prefix(n + 1, 0);
   for (int i = 0; i < n; ++i) {
     unsigned long long wus =
@@ -411,7 +618,15 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
       total_wus == 0 ? 1 : total_wus, grid_cap);
   unsigned long long* hash_out =
       reinterpret_cast<unsigned long long*>(hash_out_ptr);
-  if (gather && hash_out != nullptr) {
+  if (any_cast && hash_out != nullptr) {
+    hipLaunchKernelGGL((pack_kernel<true, true, true>), dim3(grid),
+                       dim3(kBlockThreads), 0, stream, d_descs, n, d_prefix,
+                       total_wus, flat_base, hash_out);
+  } else if (any_cast) {
+    hipLaunchKernelGGL((pack_kernel<true, false, true>), dim3(grid),
+                       dim3(kBlockThreads), 0, stream, d_descs, n, d_prefix,
+                       total_wus, flat_base, nullptr);
+  } else if (gather && hash_out != nullptr) {
     hipLaunchKernelGGL((pack_kernel<true, true>), dim3(grid),
                        dim3(kBlockThreads), 0, stream, d_descs, n, d_prefix,
                        total_wus, flat_base, hash_out);

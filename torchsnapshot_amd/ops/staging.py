@@ -95,17 +95,60 @@ class PackItem:
     outer_sizes: List[int]    # sizes of non-contiguous dims (row-major)
     outer_strides: List[int]  # byte strides of those dims
     vec: int              # safe vector width (16/8/4/2/1)
+    # narrowing cast fused into the gather (CAST_* below). With a cast,
+    # nbytes/row_bytes/flat_offset/vec are in STORED (destination) bytes;
+    # src_ptr and outer_strides stay in source bytes, and a lane reads
+    # 2*vec source bytes per vec stored bytes.
+    cast: int = 0
+
+
+CAST_NONE = 0
+CAST_F32_TO_BF16 = 1
+CAST_F32_TO_F16 = 2
+
+_CAST_CODES = {
+    (torch.float32, torch.bfloat16): CAST_F32_TO_BF16,
+    (torch.float32, torch.float16): CAST_F32_TO_F16,
+}
+
+
+def cast_code(src: torch.dtype, dst: Optional[torch.dtype]) -> int:
+    """Descriptor cast code for storing a ``src``-typed tensor as ``dst``.
+    An unsupported pair raises: a tensor is never silently left uncast."""
+    if dst is None or dst == src:
+        return CAST_NONE
+    code = _CAST_CODES.get((src, dst))
+    if code is None:
+        raise ValueError(
+            f"the gather kernel cannot cast {src} to {dst}; supported: "
+            "float32 -> bfloat16, float32 -> float16"
+        )
+    return code
 
 
 def build_pack_items(
     tensors: Sequence[torch.Tensor],
+    out_dtypes: Optional[Sequence[Optional[torch.dtype]]] = None,
 ) -> Tuple[List[PackItem], List[int], int]:
     """Compute slab layout for a batch: per-tensor descriptors, per-tensor
-    slab offsets, and total slab bytes (each tensor 256B-aligned)."""
+    slab offsets, and total slab bytes (each tensor 256B-aligned).
+    ``out_dtypes`` optionally names a stored dtype per tensor; the layout
+    (offsets, sizes, total) is then in stored bytes."""
+    if out_dtypes is None:
+        out_dtypes = [None] * len(tensors)
+    if len(out_dtypes) != len(tensors):
+        raise ValueError("out_dtypes must have one entry per tensor")
     items: List[PackItem] = []
     offsets: List[int] = []
     off = 0
-    for t in tensors:
+    for t, out_dtype in zip(tensors, out_dtypes):
+        cast = cast_code(t.dtype, out_dtype)
+        if cast != CAST_NONE:
+            item = _build_cast_item(t, out_dtype, cast, off)
+            items.append(item)
+            offsets.append(off)
+            off += (item.nbytes + ALIGN - 1) // ALIGN * ALIGN
+            continue
         nbytes = t.numel() * t.element_size()
         sizes, strides = collapse_layout(t)
         esz = t.element_size()
@@ -144,6 +187,48 @@ def build_pack_items(
     return items, offsets, off
 
 
+def _build_cast_item(
+    t: torch.Tensor, out_dtype: torch.dtype, cast: int, off: int
+) -> PackItem:
+    """Descriptor of a tensor stored as ``out_dtype``. The flat side is in
+    stored bytes; vec is the widest store (16/8/4/2 B) such that the
+    matching 2*vec-byte source read splits into naturally aligned loads
+    (two 16 B loads at vec 16, else one load of 2*vec)."""
+    if t.numel() == 0:
+        return PackItem(t.data_ptr(), off, 0, 0, [], [], 1, CAST_NONE)
+    src_esz = t.element_size()
+    dst_esz = out_dtype.itemsize
+    sizes, strides = collapse_layout(t)
+    if strides[-1] == 1:
+        row_elems = sizes[-1]
+        outer_sizes = sizes[:-1]
+        outer_strides_b = [st * src_esz for st in strides[:-1]]
+    else:
+        row_elems = 1
+        outer_sizes = sizes
+        outer_strides_b = [st * src_esz for st in strides]
+    row_bytes = row_elems * dst_esz
+    src_align = math.gcd(16, t.data_ptr())
+    for st in outer_strides_b:
+        src_align = math.gcd(src_align, st if st else 16)
+    if src_align < src_esz:
+        raise ValueError(
+            f"cannot cast-stage a {t.dtype} tensor whose address or strides "
+            f"are not {src_esz}-byte aligned"
+        )
+    vec = min(math.gcd(16, row_bytes), 16 if src_align == 16 else src_align // 2)
+    return PackItem(
+        src_ptr=t.data_ptr(),
+        flat_offset=off,
+        nbytes=t.numel() * dst_esz,
+        row_bytes=row_bytes,
+        outer_sizes=outer_sizes,
+        outer_strides=outer_strides_b,
+        vec=vec,
+        cast=cast,
+    )
+
+
 def _items_to_flat(items: List[PackItem]) -> List[int]:
     """Serialize descriptors for the extension: fixed-width int rows."""
     MAXD = 6
@@ -165,6 +250,7 @@ def _items_to_flat(items: List[PackItem]) -> List[int]:
         sizes = list(it.outer_sizes) + [1] * (MAXD - len(it.outer_sizes))
         strides = list(it.outer_strides) + [0] * (MAXD - len(it.outer_strides))
         row += sizes + strides
+        row.append(it.cast)
         flat += row
     return flat
 
@@ -380,8 +466,14 @@ class StagingEngine:
         self,
         tensors: Sequence[torch.Tensor],
         compute_checksums: bool = False,
+        out_dtypes: Optional[Sequence[Optional[torch.dtype]]] = None,
     ) -> StagedBatch:
         """Start async D2H staging of device tensors into one pinned slab.
+
+        ``out_dtypes`` optionally gives a stored dtype per tensor (None =
+        as is). A float32 tensor with a bfloat16/float16 target is narrowed
+        inside the gather kernel: offsets, sizes and checksums of the batch
+        are then those of the stored bytes. Other pairs raise ValueError.
 
         With ``compute_checksums``, the gather kernel also accumulates a
         psum64 checksum per tensor at no measurable cost (the kernel is
@@ -407,7 +499,7 @@ class StagingEngine:
             else t.contiguous()
             for t in tensors
         ]
-        items, offsets, total = build_pack_items(tensors)
+        items, offsets, total = build_pack_items(tensors, out_dtypes)
         nbytes_list = [it.nbytes for it in items]
         pinned = get_pinned_pool().acquire(max(total, 1))
         batch = StagedBatch(
@@ -427,7 +519,7 @@ class StagingEngine:
                     compute_checksums=compute_checksums,
                 )
             else:
-                self._stage_torch_fallback(tensors, items, batch)
+                self._stage_torch_fallback(tensors, items, batch, out_dtypes)
         except BaseException:
             # don't leak the pool slot on launch failure
             get_pinned_pool().release(pinned)
@@ -450,6 +542,7 @@ class StagingEngine:
             single_contig = (
                 len(items) == 1
                 and not items[0].outer_sizes
+                and items[0].cast == CAST_NONE
                 and not compute_checksums
             )
             if single_contig:
@@ -513,10 +606,15 @@ class StagingEngine:
         tensors: Sequence[torch.Tensor],
         items: List[PackItem],
         batch: StagedBatch,
+        out_dtypes: Optional[Sequence[Optional[torch.dtype]]] = None,
     ) -> None:
-        for t, it in zip(tensors, items):
+        if out_dtypes is None:
+            out_dtypes = [None] * len(items)
+        for t, it, out_dtype in zip(tensors, items, out_dtypes):
             if it.nbytes == 0:
                 continue
+            if it.cast != CAST_NONE:
+                t = t.to(out_dtype)
             flat = t.contiguous().reshape(-1).view(torch.uint8)
             dst = batch.pinned.tensor[it.flat_offset : it.flat_offset + it.nbytes]
             dst.copy_(flat, non_blocking=True)

@@ -26,7 +26,7 @@ import logging
 import threading
 import uuid
 from dataclasses import replace as dataclass_replace
-from typing import Any, Dict, List, Optional, Set, Tuple
+from typing import Any, Dict, List, Optional, Set, Tuple, Union
 
 import torch
 import torch.distributed as dist
@@ -89,6 +89,63 @@ def _match_segments(segs: List[str], pats: List[str]) -> bool:
     if not fnmatch.fnmatchcase(segs[0], head):
         return False
     return _match_segments(segs[1:], rest)
+
+
+# ---------------------------------------------------------------------------
+# save_dtype: narrowing policy for float32 leaves
+# ---------------------------------------------------------------------------
+
+SaveDtype = Union[None, torch.dtype, Dict[str, torch.dtype]]
+
+_SAVE_DTYPE_TARGETS = (torch.bfloat16, torch.float16)
+
+
+def _normalize_save_dtype(
+    save_dtype: SaveDtype,
+) -> Optional[List[Tuple[str, torch.dtype]]]:
+    """Validate ``save_dtype`` and return ordered (glob pattern, dtype)
+    rules; a bare dtype means {"**": dtype}. Raises before any I/O."""
+    if save_dtype is None:
+        return None
+    if isinstance(save_dtype, torch.dtype):
+        rules = [("**", save_dtype)]
+    elif isinstance(save_dtype, dict):
+        rules = list(save_dtype.items())
+    else:
+        raise ValueError(
+            "save_dtype must be a torch.dtype or a dict of glob pattern -> "
+            f"torch.dtype, got {type(save_dtype).__name__}"
+        )
+    for pattern, dtype in rules:
+        if not isinstance(pattern, str):
+            raise ValueError(f"save_dtype pattern must be a str, got {pattern!r}")
+        if dtype not in _SAVE_DTYPE_TARGETS:
+            raise ValueError(
+                f"save_dtype target {dtype!r} (pattern '{pattern}') is not "
+                "supported; allowed: torch.bfloat16, torch.float16"
+            )
+    return rules
+
+
+def _resolve_save_dtype(
+    rules: Optional[List[Tuple[str, torch.dtype]]],
+    logical_path: str,
+    obj: Any,
+) -> Optional[torch.dtype]:
+    """Stored dtype for one leaf, or None to store it unchanged. Only
+    strided, non-quantized float32 tensors are narrowed (DTensor and
+    ShardedTensor qualify through their local shards)."""
+    if not rules or not isinstance(obj, torch.Tensor):
+        return None
+    if obj.dtype != torch.float32:
+        return None
+    if type(obj) is torch.Tensor or isinstance(obj, torch.nn.Parameter):
+        if obj.is_quantized or obj.layout != torch.strided:
+            return None
+    for pattern, dtype in rules:
+        if glob_match(logical_path, pattern):
+            return dtype
+    return None
 
 
 # ---------------------------------------------------------------------------
@@ -180,9 +237,16 @@ class Snapshot:
         replicated: Optional[List[str]] = None,
         storage_options: Optional[Dict[str, Any]] = None,
         _custom_tensor_prepare_func: Optional[Any] = None,
+        save_dtype: SaveDtype = None,
     ) -> "Snapshot":
+        """``save_dtype``: store float32 tensors narrowed to
+        ``torch.bfloat16`` / ``torch.float16`` — one dtype for everything,
+        or a dict from glob pattern (over logical paths; first match wins)
+        to dtype. Device tensors are cast inside the staging gather kernel;
+        leaves that are not strided float32 tensors are stored unchanged."""
         torch._C._log_api_usage_once("torchsnapshot_amd.Snapshot.take")
         cls._validate_app_state(app_state)
+        save_dtype_rules = _normalize_save_dtype(save_dtype)
         pg_wrapper = PGWrapper(pg)
         unique_id = uuid.uuid4().hex
         event_meta = {"id": unique_id, "rank": pg_wrapper.get_rank(), "api": "take"}
@@ -201,6 +265,7 @@ class Snapshot:
                     replicated=replicated,
                     is_async=False,
                     custom_tensor_prepare_func=_custom_tensor_prepare_func,
+                    save_dtype_rules=save_dtype_rules,
                 )
                 pending_io_work.complete()
                 from .integrity import write_checksum_file
@@ -228,9 +293,12 @@ class Snapshot:
         replicated: Optional[List[str]] = None,
         storage_options: Optional[Dict[str, Any]] = None,
         _custom_tensor_prepare_func: Optional[Any] = None,
+        save_dtype: SaveDtype = None,
     ) -> "PendingSnapshot":
+        """See :meth:`take` for ``save_dtype``."""
         torch._C._log_api_usage_once("torchsnapshot_amd.Snapshot.async_take")
         cls._validate_app_state(app_state)
+        save_dtype_rules = _normalize_save_dtype(save_dtype)
         pg_wrapper = PGWrapper(pg)
         unique_id = uuid.uuid4().hex
         event_meta = {
@@ -263,6 +331,7 @@ class Snapshot:
                 replicated=replicated,
                 is_async=True,
                 custom_tensor_prepare_func=_custom_tensor_prepare_func,
+                save_dtype_rules=save_dtype_rules,
             )
             # once staging is complete, the app may mutate its state
             # freely. With shadow clones (sources_immutable) there is
@@ -301,6 +370,7 @@ class Snapshot:
         replicated: List[str],
         is_async: bool,
         custom_tensor_prepare_func: Optional[Any] = None,
+        save_dtype_rules: Optional[List[Tuple[str, torch.dtype]]] = None,
     ) -> Tuple[PendingIOWork, SnapshotMetadata]:
         rank = pg_wrapper.get_rank()
         world_size = pg_wrapper.get_world_size()
@@ -359,6 +429,11 @@ class Snapshot:
         seen_tensors: Dict[Any, Entry] = {}
         for logical_path, obj in flattened.items():
             alias_key = None
+            # shadow clones above stay in the source dtype; the narrowing
+            # happens at staging time
+            target_dtype = _resolve_save_dtype(
+                save_dtype_rules, logical_path, obj
+            )
             if (
                 isinstance(obj, torch.Tensor)
                 and type(obj) is torch.Tensor
@@ -372,6 +447,7 @@ class Snapshot:
                     tuple(obj.stride()),
                     str(obj.device),
                     logical_path in replicated_paths,
+                    target_dtype,
                 )
                 if alias_key in seen_tensors:
                     manifest[logical_path] = seen_tensors[alias_key]
@@ -382,6 +458,7 @@ class Snapshot:
                 rank=rank,
                 replicated=logical_path in replicated_paths,
                 is_async_snapshot=is_async,
+                save_dtype=target_dtype,
             )
             manifest[logical_path] = entry
             if alias_key is not None:
