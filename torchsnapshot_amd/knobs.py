@@ -137,6 +137,17 @@ def get_storage_write_chunk_bytes() -> int:
     return _env_bytes("TSAMD_FS_WRITE_CHUNK_BYTES", 256 * _MB)
 
 
+def is_fs_reuse_pages_enabled() -> bool:
+    """Re-saving onto an existing payload file of at least 1 MiB overwrites
+    it in place (no O_TRUNC), so the file's page-cache pages are reused
+    instead of freed and reallocated. ``TSAMD_FS_REUSE_PAGES=0`` restores
+    truncate-and-rewrite; read per write, so both policies can be compared
+    in one process. Durable saves (``TSAMD_FSYNC=1``) always truncate."""
+    return os.environ.get("TSAMD_FS_REUSE_PAGES", "1") not in (
+        "0", "", "false", "False"
+    )
+
+
 def get_fs_parallel_io_min_bytes() -> int:
     """Files at/above this size are READ as concurrent segments (multiple
     NVMe queues per file; closes the cold-read gap vs raw device bandwidth

@@ -17,6 +17,9 @@ from pathlib import Path
 
 PKG_ROOT = Path(__file__).resolve().parent.parent
 SRC = PKG_ROOT / "ops" / "hip" / "staging.hip"
+# everything the translation unit reads: the extension is rebuilt when any
+# of these is newer than it
+DEPS = (SRC, PKG_ROOT / "ops" / "hip" / "file_sink.h")
 OUT = PKG_ROOT / f"_csnap{sysconfig.get_config_var('EXT_SUFFIX') or '.so'}"
 
 GFX_ARCH = os.environ.get("TSAMD_GFX_ARCH", "gfx950")
@@ -31,7 +34,8 @@ def _pybind11_includes() -> list[str]:
 def needs_rebuild() -> bool:
     if not OUT.exists():
         return True
-    return SRC.stat().st_mtime > OUT.stat().st_mtime
+    built = OUT.stat().st_mtime
+    return any(dep.stat().st_mtime > built for dep in DEPS)
 
 
 def build(force: bool = False, verbose: bool = True) -> Path:

@@ -41,6 +41,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "file_sink.h"
+
 namespace py = pybind11;
 
 #define HIP_CHECK(expr)                                                     \
@@ -839,6 +841,43 @@ static unsigned long long psum64_host(py::buffer b,
   return total;
 }
 
+// Storage payload write (ops/hip/file_sink.h): open, pwrite loop, optional
+// fsync and close in one GIL-free call. Returns true when the existing
+// file's pages were reused (no O_TRUNC).
+static bool file_write(py::object path, py::object buf, bool fsync,
+                       long long chunk_bytes, bool reuse) {
+  if (chunk_bytes <= 0) {
+    throw py::value_error("file_write: chunk_bytes must be positive");
+  }
+  // str / bytes / os.PathLike -> filesystem-encoded bytes
+  PyObject* fs_bytes = nullptr;
+  if (!PyUnicode_FSConverter(path.ptr(), &fs_bytes)) {
+    throw py::error_already_set();
+  }
+  std::string cpath(PyBytes_AS_STRING(fs_bytes),
+                    (size_t)PyBytes_GET_SIZE(fs_bytes));
+  Py_DECREF(fs_bytes);
+  // PyBUF_SIMPLE: any C-contiguous exporter, read-only ones included;
+  // a non-contiguous view raises BufferError here
+  Py_buffer view;
+  if (PyObject_GetBuffer(buf.ptr(), &view, PyBUF_SIMPLE) != 0) {
+    throw py::error_already_set();
+  }
+  tsamd::SinkResult res;
+  {
+    py::gil_scoped_release release;
+    res = tsamd::file_write(cpath, view.buf, (size_t)view.len, fsync,
+                            (size_t)chunk_bytes, reuse);
+  }
+  PyBuffer_Release(&view);
+  if (res.err) {
+    errno = res.err;
+    PyErr_SetFromErrnoWithFilenameObject(PyExc_OSError, path.ptr());
+    throw py::error_already_set();
+  }
+  return res.reused;
+}
+
 static void op_wait(long long handle) {
   hipEvent_t ev = nullptr;
   int device = 0;
@@ -945,6 +984,11 @@ PYBIND11_MODULE(_csnap, m) {
         "psum64 of a flat contiguous device buffer (blocking)",
         py::arg("ptr"), py::arg("nbytes"), py::arg("byte0"),
         py::arg("producer_stream"), py::arg("device"));
+  m.def("file_write", &file_write,
+        "write a buffer to a file (GIL released); reuse=True overwrites an "
+        "existing file of >= 1 MiB payload in place instead of truncating",
+        py::arg("path"), py::arg("buf"), py::arg("fsync") = false,
+        py::arg("chunk_bytes") = 256ll * 1024 * 1024, py::arg("reuse") = true);
   m.def("wait", &op_wait, "block until an op completes");
   m.def("query", &op_query, "poll an op");
   m.def("is_managed_ptr", &is_managed_ptr);

@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import fnmatch
 import logging
+import os
 import threading
 import uuid
 from dataclasses import replace as dataclass_replace
@@ -476,6 +477,14 @@ class Snapshot:
 
         write_reqs = _batch(write_reqs, rank)
 
+        # A re-save overwrites payload files in place (storage/fs.py), so
+        # the old commit must go first: otherwise a save that dies half-way
+        # leaves the old metadata pointing at half-new payloads of
+        # plausible length. The manifest all-gather below orders this
+        # before any rank's first payload write.
+        if rank == 0:
+            cls._uncommit(storage)
+
         global_manifest = cls._gather_manifest(manifest, pg_wrapper)
         metadata = SnapshotMetadata(
             version=__version__,
@@ -489,6 +498,21 @@ class Snapshot:
         )
         pending.sources_immutable = sources_immutable
         return pending, metadata
+
+    @staticmethod
+    def _uncommit(storage: StoragePlugin) -> None:
+        """Remove an existing ``.snapshot_metadata`` under a filesystem
+        snapshot path (a missing one is fine). Object stores replace whole
+        objects and never expose a half-written one, so only the FS plugin
+        needs this."""
+        from .storage.fs import FSStoragePlugin
+
+        if not isinstance(storage, FSStoragePlugin):
+            return
+        try:
+            os.remove(os.path.join(storage.root, METADATA_FILENAME))
+        except FileNotFoundError:
+            pass
 
     @classmethod
     def _shadow_for_async(cls, flattened: Flattened) -> bool:

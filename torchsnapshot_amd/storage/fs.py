@@ -18,13 +18,20 @@ torchsnapshot/storage_plugins/fs.py:28-51, via a different mechanism).
 from __future__ import annotations
 
 import asyncio
+import errno
 import os
 import shutil
+import stat
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional, Set
 
 from .. import knobs
 from ..io_types import ReadIO, StoragePlugin, WriteIO
+
+try:
+    from torchsnapshot_amd import _csnap  # compiled extension (file_write)
+except ImportError:  # not built: the Python writer below takes over
+    _csnap = None
 
 
 def _fsync_enabled() -> bool:
@@ -40,6 +47,93 @@ def _as_u8_mv(buf) -> memoryview:
     if mv.format != "B":
         mv = mv.cast("B")
     return mv
+
+
+# Payloads of at least this many bytes overwrite an existing file in place
+# (kReuseMinBytes in ops/hip/file_sink.h; keep the two equal).
+REUSE_MIN_BYTES = 1 << 20
+
+
+def _fsync_file_and_dir(fd: int, full: str) -> None:
+    os.fsync(fd)
+    # make the directory entry durable too (crash consistency: the
+    # metadata commit must never be durable before its payloads)
+    dfd = os.open(os.path.dirname(full) or ".", os.O_RDONLY)
+    try:
+        os.fsync(dfd)
+    finally:
+        os.close(dfd)
+
+
+def _write_file_py(
+    full: str, buf, fsync: bool, chunk_bytes: int, reuse: bool
+) -> bool:
+    """Pure-Python payload writer; same policy, byte for byte, as the
+    native one (ops/hip/file_sink.h). Returns True when an existing file
+    was overwritten in place."""
+    if chunk_bytes <= 0:
+        raise ValueError("chunk_bytes must be positive")
+    mv = _as_u8_mv(buf)
+    total = len(mv)
+    fd = -1
+    old_size = 0
+    reused = False
+    if reuse and total >= REUSE_MIN_BYTES:
+        try:
+            fd = os.open(full, os.O_WRONLY)
+        except FileNotFoundError:
+            fd = -1
+        if fd >= 0:
+            try:
+                st = os.fstat(fd)
+            except BaseException:
+                os.close(fd)
+                raise
+            if stat.S_ISREG(st.st_mode):
+                old_size = st.st_size
+                reused = True
+            else:
+                os.close(fd)
+                fd = -1
+    if fd < 0:
+        fd = os.open(full, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+    try:
+        off = 0
+        while off < total:
+            n = os.pwrite(fd, mv[off : off + chunk_bytes], off)
+            if n == 0:
+                raise OSError(errno.EIO, os.strerror(errno.EIO), full)
+            off += n
+        if reused and old_size > total:
+            os.ftruncate(fd, total)
+        if fsync:
+            _fsync_file_and_dir(fd, full)
+    finally:
+        os.close(fd)
+    return reused
+
+
+def _write_file_native(
+    full: str, buf, fsync: bool, chunk_bytes: int, reuse: bool
+) -> bool:
+    """open + pwrite loop + optional fsync + close in one GIL-free call of
+    the compiled extension."""
+    return _csnap.file_write(
+        full, buf, fsync=fsync, chunk_bytes=chunk_bytes, reuse=reuse
+    )
+
+
+def write_file(
+    full: str, buf, fsync: bool, chunk_bytes: int, reuse: bool
+) -> bool:
+    """Write one payload file, one sequential stream. With ``reuse``, a
+    payload of at least 1 MiB landing on an existing regular file
+    overwrites it in place and trims a longer old tail, which keeps the
+    file's page-cache pages; everything else is create-or-truncate. Uses
+    the native writer when the extension is built."""
+    if _csnap is not None:
+        return _write_file_native(full, buf, fsync, chunk_bytes, reuse)
+    return _write_file_py(full, buf, fsync, chunk_bytes, reuse)
 
 
 class FSStoragePlugin(StoragePlugin):
@@ -63,36 +157,26 @@ class FSStoragePlugin(StoragePlugin):
         os.makedirs(dirname, exist_ok=True)
         self._created_dirs.add(dirname)
 
-    def _fsync_file_and_dir(self, fd: int, full: str) -> None:
-        os.fsync(fd)
-        # make the directory entry durable too (crash consistency: the
-        # metadata commit must never be durable before its payloads)
-        dfd = os.open(os.path.dirname(full), os.O_RDONLY)
-        try:
-            os.fsync(dfd)
-        finally:
-            os.close(dfd)
-
     def _write_sync(self, path: str, buf) -> None:
         full = self._abspath(path)
         self._ensure_dir(os.path.dirname(full))
-        mv = _as_u8_mv(buf)
-        fd = os.open(full, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
-        try:
-            chunk = knobs.get_storage_write_chunk_bytes()
-            off = 0
-            total = len(mv)
-            while off < total:
-                off += os.pwrite(fd, mv[off : off + chunk], off)
-            if _fsync_enabled():
-                self._fsync_file_and_dir(fd, full)
-            # note: fadvise(DONTNEED) after payload writes was measured
-            # and rejected — it did not lift the sustained save rate
-            # (9.50 vs 9.40 GB/s, writeback equilibrium dominates either
-            # way) and it cost warm restores 3x (50 -> 16 GB/s).
-            # profiles/r02_measurements.md.
-        finally:
-            os.close(fd)
+        fsync = _fsync_enabled()
+        write_file(
+            full,
+            buf,
+            fsync=fsync,
+            chunk_bytes=knobs.get_storage_write_chunk_bytes(),
+            # Durable saves keep truncate-and-rewrite: after an fsync'd save
+            # the old pages are clean, so truncation waits for nothing and
+            # the save is bound by the disk either way (measured: in-place
+            # 8.4-9.0 GB/s, truncate 8.5-9.6;
+            # profiles/native_write_measurements.md).
+            reuse=knobs.is_fs_reuse_pages_enabled() and not fsync,
+        )
+        # note: fadvise(DONTNEED) after payload writes was measured and
+        # rejected — it did not lift the sustained save rate (9.50 vs
+        # 9.40 GB/s) and it cost warm restores 3x (50 -> 16 GB/s).
+        # profiles/r02_measurements.md.
 
     def _pread_segment(
         self, full: str, mv: memoryview, file_off: int
