@@ -315,6 +315,43 @@ class BatchedBufferConsumer(BufferConsumer):
                 return None
         return device
 
+    def _scatter_members(self):
+        """StagingEngine.scatter members for the whole span, or None when
+        the span takes the H2D + per-member copy path instead. Members opt
+        in with ``scatter_members(base_offset, verified) -> list | None``
+        (targets they already hold as results, so nothing is left to do
+        after the launch); one member answering None, or a target on
+        another device, sends the whole span down the other path."""
+        verified = self.expected_psum is not None
+        if verified and not self._members_tile_span():
+            return None
+        device = self._device_fast_path_target()
+        out = []
+        for m in self.members:
+            getter = getattr(m.consumer, "scatter_members", None)
+            sub = (
+                getter(m.byte_range[0] - self.span_start, verified)
+                if getter
+                else None
+            )
+            if sub is None or any(t.device != device for t, _, _ in sub):
+                return None
+            out.extend(sub)
+        return out
+
+    def _members_tile_span(self) -> bool:
+        """The span's expected checksum sums every recorded slab member
+        inside it, read or not, while the scatter kernel hashes only the
+        bytes it scatters. The two agree when the members read tile the
+        span up to slab padding: a gap below ALIGN cannot hold another
+        member (they start ALIGN-aligned), and padding is zero."""
+        pos = self.span_start
+        for s, e in sorted(m.byte_range for m in self.members):
+            if s < pos or s - pos >= ALIGN:
+                return False
+            pos = e
+        return True
+
     def will_verify_on_device(self) -> bool:
         from .ops.staging import HIP_EXT_AVAILABLE
 
@@ -331,7 +368,23 @@ class BatchedBufferConsumer(BufferConsumer):
             return
 
         def work() -> None:
+            what = (
+                f"{self.members[0].path} span[{self.span_start}:"
+                f"{self.span_start + memoryview(buf).nbytes}]"
+            )
             if self._pinned_block is not None:
+                members = self._scatter_members()
+                if members is not None:
+                    # the whole span in ONE scatter launch, straight out of
+                    # the pinned block
+                    get_staging_engine(device).scatter(
+                        self._pinned_block,
+                        self._pinned_nbytes,
+                        members,
+                        expected_psum=self.expected_psum,
+                        what=what,
+                    )
+                    return
                 # read landed in pinned memory already: straight SDMA H2D
                 n = self._pinned_nbytes
                 dev_span = self._pinned_block.tensor[:n].to(
@@ -353,12 +406,7 @@ class BatchedBufferConsumer(BufferConsumer):
             if self.expected_psum is not None:
                 from .ops.staging import verify_device_psum
 
-                verify_device_psum(
-                    dev_span,
-                    self.expected_psum,
-                    f"{self.members[0].path} span[{self.span_start}:"
-                    f"{self.span_start + memoryview(buf).nbytes}]",
-                )
+                verify_device_psum(dev_span, self.expected_psum, what)
             for m in self.members:
                 s, e = m.byte_range
                 sub = dev_span[s - self.span_start : e - self.span_start]

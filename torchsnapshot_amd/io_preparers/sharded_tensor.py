@@ -29,6 +29,7 @@ from ..io_types import (
 from ..manifest import Shard as ShardMeta
 from ..manifest import ShardedTensorEntry, TensorEntry
 from ..serialization import (
+    SERIALIZER_BUFFER,
     dtype_to_str,
     str_to_dtype,
     tensor_from_memoryview,
@@ -80,6 +81,21 @@ def narrow_nd(
     for dim, (off, ln) in enumerate(zip(offsets, lengths)):
         view = view.narrow(dim, off, ln)
     return view
+
+
+def contiguous_source_offset(
+    shard_shape: Sequence[int], overlap: "Overlap"
+) -> Optional[int]:
+    """Element offset of the overlap's source box within the stored shard
+    when the box is one contiguous run of it (same-sharding restores, dim-0
+    resharding), else None (a general N-d sub-box). Asked of a meta tensor,
+    so the answer is torch's own notion of contiguity."""
+    box = narrow_nd(
+        torch.empty(tuple(shard_shape), device="meta"),
+        overlap.src_offsets,
+        overlap.lengths,
+    )
+    return box.storage_offset() if box.is_contiguous() else None
 
 
 def subdivide_shard(
@@ -175,6 +191,42 @@ class ShardConsumer(BufferConsumer):
             and self.shard_entry.serializer != "torch_save"
         )
 
+    def scatter_members(self, base_offset: int, verified: bool = False):
+        """StagingEngine.scatter members that restore this shard from a
+        pinned read whose byte ``base_offset`` is the shard's first, or
+        None when it needs the torch path: every overlap's source box has
+        to be a contiguous run of the stored shard, every target eligible
+        and on one device. A ``verified`` (checksummed) scatter hashes only
+        what it scatters, so the members must then cover the shard's bytes
+        exactly once."""
+        from ..ops.staging import scatter_member
+
+        if self.shard_entry.serializer != SERIALIZER_BUFFER or not self.targets:
+            return None
+        stored = str_to_dtype(self.shard_entry.dtype)
+        device = self.targets[0][0].device
+        members = []
+        for dst_view, ov in self.targets:
+            src_off = contiguous_source_offset(self.shard_entry.shape, ov)
+            if src_off is None or dst_view.device != device:
+                return None
+            dst = narrow_nd(dst_view.detach(), ov.dst_offsets, ov.lengths)
+            member = scatter_member(
+                dst, stored, base_offset + src_off * stored.itemsize
+            )
+            if member is None:
+                return None
+            members.append(member)
+        if verified:
+            pos = base_offset
+            for dst, _, off in sorted(members, key=lambda m: m[2]):
+                if off != pos:
+                    return None
+                pos += dst.numel() * stored.itemsize
+            if pos - base_offset != self.shard_entry.nbytes_estimate():
+                return None
+        return members
+
     def consume_from_device_u8(self, dev_u8: torch.Tensor) -> None:
         dtype = str_to_dtype(self.shard_entry.dtype)
         shard = (
@@ -192,9 +244,25 @@ class ShardConsumer(BufferConsumer):
             if self.shard_entry.serializer == "torch_save":
                 shard = torch_load_from_bytes(bytes(buf))
             elif self._pinned_block is not None and self.all_targets_on_device():
+                n = self._pinned_nbytes
+                members = self.scatter_members(
+                    0, verified=self.expected_psum is not None
+                )
+                if members is not None:
+                    # every overlap in one scatter launch, straight out of
+                    # the pinned block
+                    from ..ops.staging import get_staging_engine
+
+                    get_staging_engine(self.targets[0][0].device).scatter(
+                        self._pinned_block,
+                        n,
+                        members,
+                        expected_psum=self.expected_psum,
+                        what=self.shard_entry.location,
+                    )
+                    return
                 # storage read landed in pinned memory: straight SDMA H2D,
                 # overlap scatter runs on the GPU
-                n = self._pinned_nbytes
                 dtype = str_to_dtype(self.shard_entry.dtype)
                 dev_u8 = self._pinned_block.tensor[:n].to(
                     self.targets[0][0].device, non_blocking=False

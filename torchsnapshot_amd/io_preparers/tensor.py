@@ -450,6 +450,27 @@ class TensorBufferConsumer(BufferConsumer):
             and self.entry.serializer == SERIALIZER_BUFFER
         )
 
+    def scatter_members(self, base_offset: int, verified: bool = False):
+        """Batched-span member protocol: the StagingEngine.scatter members
+        that restore this consumer from a pinned read whose byte
+        ``base_offset`` is the payload's first, or None when it needs the
+        torch path. The one member covers the payload exactly once, which
+        is what a ``verified`` (checksummed) scatter asks for."""
+        from ..ops.staging import scatter_member
+
+        out = self.tensor_out
+        if (
+            out is None
+            or self.entry.serializer != SERIALIZER_BUFFER
+            # copy_ would broadcast a differently shaped payload
+            or list(out.shape) != list(self.entry.shape)
+        ):
+            return None
+        member = scatter_member(
+            out.detach(), str_to_dtype(self.entry.dtype), base_offset
+        )
+        return None if member is None else [member]
+
     def consume_from_device_u8(self, dev_u8: torch.Tensor) -> None:
         dtype = str_to_dtype(self.entry.dtype)
         loaded = (
@@ -476,8 +497,24 @@ class TensorBufferConsumer(BufferConsumer):
                 and self.tensor_out is not None
                 and self.tensor_out.device.type == "cuda"
             ):
-                # buffer already lives in pinned memory: straight SDMA H2D
                 n = self._pinned_nbytes
+                members = self.scatter_members(0)
+                if members is not None:
+                    # one scatter launch straight out of the pinned block:
+                    # no device-side copy of the payload, widening and the
+                    # checksum fused in
+                    from ..ops.staging import get_staging_engine
+
+                    get_staging_engine(self.tensor_out.device).scatter(
+                        self._pinned_block,
+                        n,
+                        members,
+                        expected_psum=self.expected_psum,
+                        what=self.entry.location,
+                    )
+                    self.fut.obj = self.tensor_out
+                    return
+                # buffer already lives in pinned memory: straight SDMA H2D
                 dev_u8 = self._pinned_block.tensor[:n].to(
                     self.tensor_out.device, non_blocking=False
                 )

@@ -116,6 +116,24 @@ def is_hip_staging_disabled() -> bool:
     return _env_flag("TSAMD_DISABLE_HIP_STAGING")
 
 
+def get_restore_mode() -> str:
+    """How pinned payload bytes reach device targets on restore.
+    "direct": one scatter kernel per read pulls them straight out of pinned
+    host memory (no transient HBM). "slab": one H2D copy into a device slab
+    of the payload's size, then one scatter kernel. "torch" (default): the
+    pre-kernel path, ``.to(device)`` plus one ``copy_`` per member. On the
+    flagship restore neither kernel mode's median reached the torch path's
+    slowest run (profiles/restore_scatter_measurements.md), so the kernel
+    modes are opt-in: "direct" for restoring onto a nearly full GPU,
+    either for save_dtype snapshots (no stored-dtype temporary)."""
+    mode = os.environ.get("TSAMD_RESTORE_MODE", "torch")
+    if mode not in ("direct", "slab", "torch"):
+        raise ValueError(
+            f"TSAMD_RESTORE_MODE must be direct|slab|torch, got {mode}"
+        )
+    return mode
+
+
 def get_async_shadow_mode() -> str:
     """Shadow-clone async snapshots: "auto" (default) clones device
     tensors at HBM rate before async_take returns, when free HBM allows —

@@ -9,7 +9,8 @@
 //     :104-162, and its tensor.cpu() staging, io_preparers/tensor.py:353)
 //   - gather-and-cast: per-descriptor f32 -> bf16/f16 narrowing fused into
 //     the same launch (save_dtype), so only stored-size bytes leave the GPU
-//   - scatter kernel (same code path, direction-reversed) for restore
+//   - scatter kernel (same code path, direction-reversed) for restore, with
+//     bf16/f16 -> f32 widening and the psum64 check fused into the launch
 //   - SDMA copies (hipMemcpyAsync) slab <-> pinned host memory; the slab
 //     can also be skipped entirely ("direct" mode): the kernel writes
 //     gathered bytes straight into pinned host memory over PCIe
@@ -74,12 +75,17 @@ struct Desc {
   // With a cast, every flat-side quantity above (nbytes, row_bytes,
   // flat_off, vec) is in DESTINATION bytes; tensor_base and strides stay
   // in source bytes. A lane writes `vec` bytes and reads 2*vec.
+  // Scatter only: 3 bf16->f32, 4 f16->f32 widening, same convention (flat
+  // side in stored 2-byte units, tensor side in f32 bytes): a lane reads
+  // `vec` stored bytes and writes 2*vec.
   uint32_t cast;
 };
 
 constexpr uint32_t kCastNone = 0;
 constexpr uint32_t kCastBF16 = 1;
 constexpr uint32_t kCastF16 = 2;
+constexpr uint32_t kCastBF16toF32 = 3;
+constexpr uint32_t kCastF16toF32 = 4;
 
 // ---------------------------------------------------------------------------
 // psum64 checksum: an order-independent weighted word sum over the flat
@@ -165,11 +171,55 @@ __device__ inline void copy_vec(char* flat, const char* strided) {
   }
 }
 
+// Scatter VEC flat bytes into the strided tensor. When HASH, returns the
+// psum64 contribution of those bytes, computed from the registers just
+// loaded: the flat side may be uncached host memory across PCIe and is
+// read exactly once.
+template <int VEC, bool HASH>
+__device__ inline unsigned long long scatter_vec(
+    char* strided, const char* flat, unsigned long long file_off) {
+  unsigned long long h = 0;
+  if (VEC == 16) {
+    const uint4 a = *reinterpret_cast<const uint4*>(flat);
+    *reinterpret_cast<uint4*>(strided) = a;
+    if (HASH) {
+      unsigned long long w = file_off >> 3;
+      h += (((unsigned long long)a.y << 32) | a.x) * psum_mult(w);
+      h += (((unsigned long long)a.w << 32) | a.z) * psum_mult(w + 1);
+    }
+  } else if (VEC == 8) {
+    const unsigned long long a =
+        *reinterpret_cast<const unsigned long long*>(flat);
+    *reinterpret_cast<unsigned long long*>(strided) = a;
+    if (HASH) h += a * psum_mult(file_off >> 3);
+  } else {
+    unsigned long long v;
+    if (VEC == 4) {
+      const uint32_t a = *reinterpret_cast<const uint32_t*>(flat);
+      *reinterpret_cast<uint32_t*>(strided) = a;
+      v = a;
+    } else if (VEC == 2) {
+      const uint16_t a = *reinterpret_cast<const uint16_t*>(flat);
+      *reinterpret_cast<uint16_t*>(strided) = a;
+      v = a;
+    } else {
+      const unsigned char a = *reinterpret_cast<const unsigned char*>(flat);
+      *reinterpret_cast<unsigned char*>(strided) = a;
+      v = a;
+    }
+    if (HASH) h += (v << (8 * (file_off & 7))) * psum_mult(file_off >> 3);
+  }
+  return h;
+}
+
 // Copy [s, e) of the tensor's flat byte range for one work unit. When
-// HASH (gather only), returns this thread's psum64 contribution.
+// HASH, returns this thread's psum64 contribution. Gather hashes at slab
+// offsets (d.flat_off); scatter hashes at `hash_off`, the file offset of
+// the descriptor's first flat byte.
 template <int VEC, bool GATHER, bool HASH>
 __device__ unsigned long long process_range(const Desc& d, char* flat_base,
-                                            uint32_t s, uint32_t e) {
+                                            uint32_t s, uint32_t e,
+                                            unsigned long long hash_off = 0) {
   char* flat = flat_base + d.flat_off;
   const uint32_t tid = threadIdx.x;
   const uint32_t rb = d.row_bytes;
@@ -178,8 +228,13 @@ __device__ unsigned long long process_range(const Desc& d, char* flat_base,
     // fully contiguous: plain vectorized copy of [s, e)
     const char* src = d.tensor_base;
     for (uint32_t i = s + tid * VEC; i < e; i += kBlockThreads * VEC) {
-      copy_vec<VEC, GATHER>(flat + i, src + i);
-      if (HASH) h += psum_contrib<VEC>(src + i, d.flat_off + i);
+      if (GATHER) {
+        copy_vec<VEC, GATHER>(flat + i, src + i);
+        if (HASH) h += psum_contrib<VEC>(src + i, d.flat_off + i);
+      } else {
+        h += scatter_vec<VEC, HASH>(const_cast<char*>(src) + i, flat + i,
+                                    hash_off + i);
+      }
     }
     return h;
   }
@@ -192,8 +247,13 @@ __device__ unsigned long long process_range(const Desc& d, char* flat_base,
       const char* src = d.tensor_base + row_offset(d, row);
       uint32_t n = min(rb - col, e - off);
       for (uint32_t i = tid * VEC; i < n; i += kBlockThreads * VEC) {
-        copy_vec<VEC, GATHER>(flat + off + i, src + col + i);
-        if (HASH) h += psum_contrib<VEC>(src + col + i, d.flat_off + off + i);
+        if (GATHER) {
+          copy_vec<VEC, GATHER>(flat + off + i, src + col + i);
+          if (HASH) h += psum_contrib<VEC>(src + col + i, d.flat_off + off + i);
+        } else {
+          h += scatter_vec<VEC, HASH>(const_cast<char*>(src) + col + i,
+                                      flat + off + i, hash_off + off + i);
+        }
       }
       off += n;
       ++row;
@@ -209,8 +269,14 @@ __device__ unsigned long long process_range(const Desc& d, char* flat_base,
       uint32_t lo = flat_pos < s ? (s - flat_pos) : 0;
       uint32_t hi = (flat_pos + rb > e) ? (e - flat_pos) : rb;
       for (uint32_t i = lo; i < hi; i += VEC) {
-        copy_vec<VEC, GATHER>(flat + flat_pos + i, src + i);
-        if (HASH) h += psum_contrib<VEC>(src + i, d.flat_off + flat_pos + i);
+        if (GATHER) {
+          copy_vec<VEC, GATHER>(flat + flat_pos + i, src + i);
+          if (HASH) h += psum_contrib<VEC>(src + i, d.flat_off + flat_pos + i);
+        } else {
+          h += scatter_vec<VEC, HASH>(const_cast<char*>(src) + i,
+                                      flat + flat_pos + i,
+                                      hash_off + flat_pos + i);
+        }
       }
     }
   }
@@ -421,6 +487,201 @@ __global__ __launch_bounds__(kBlockThreads) void pack_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// scatter-and-widen (bf16 / f16 -> f32), the restore half of save_dtype.
+// Exact integer bit arithmetic like the narrowing above: no dependence on
+// the wave's denormal mode, f16 subnormals renormalise exactly.
+// ---------------------------------------------------------------------------
+
+__device__ __host__ inline uint32_t bf16_to_f32_bits(uint32_t b) {
+  return b << 16;  // every pattern, NaN payloads included
+}
+
+__device__ __host__ inline uint32_t f16_to_f32_bits(uint32_t h) {
+  const uint32_t sign = (h & 0x8000u) << 16;
+  const uint32_t exp = (h >> 10) & 0x1Fu;
+  const uint32_t mant = h & 0x03FFu;
+  if (exp == 0x1Fu) {
+    // inf keeps a zero mantissa; NaN turns quiet, payload kept
+    return sign | 0x7F800000u | (mant << 13) | (mant ? 0x00400000u : 0u);
+  }
+  if (exp != 0u) return sign | ((exp + 112u) << 23) | (mant << 13);
+  if (mant == 0u) return sign;  // +-0
+  // subnormal: mant * 2^-24. Shift the leading one up to bit 10 (the
+  // implicit bit); each position shifted lowers the exponent from 2^-14
+  const uint32_t shift = (uint32_t)__builtin_clz(mant) - 21u;  // 1..10
+  return sign | ((113u - shift) << 23) | (((mant << shift) & 0x03FFu) << 13);
+}
+
+__device__ inline uint2 widen_pair(uint32_t packed, uint32_t code) {
+  // two 16-bit patterns packed little-endian -> two f32 bit patterns
+  uint2 o;
+  if (code == kCastBF16toF32) {
+    o.x = bf16_to_f32_bits(packed & 0xFFFFu);
+    o.y = packed & 0xFFFF0000u;
+  } else {
+    o.x = f16_to_f32_bits(packed & 0xFFFFu);
+    o.y = f16_to_f32_bits(packed >> 16);
+  }
+  return o;
+}
+
+// Convert VEC stored bytes at `flat` into 2*VEC bytes at `dst`. Every load
+// and store is naturally aligned to its own width (the host picks vec so).
+// When HASH, returns the psum64 contribution of the STORED bytes, taken
+// from the registers the conversion reads.
+template <int VEC, bool HASH>
+__device__ inline unsigned long long widen_vec(char* dst, const char* flat,
+                                               uint32_t code,
+                                               unsigned long long file_off) {
+  unsigned long long h = 0;
+  if (VEC == 16) {
+    const uint4 a = *reinterpret_cast<const uint4*>(flat);
+    const uint2 p0 = widen_pair(a.x, code), p1 = widen_pair(a.y, code);
+    const uint2 p2 = widen_pair(a.z, code), p3 = widen_pair(a.w, code);
+    *reinterpret_cast<uint4*>(dst) = make_uint4(p0.x, p0.y, p1.x, p1.y);
+    *reinterpret_cast<uint4*>(dst + 16) = make_uint4(p2.x, p2.y, p3.x, p3.y);
+    if (HASH) {
+      unsigned long long w = file_off >> 3;
+      h += (((unsigned long long)a.y << 32) | a.x) * psum_mult(w);
+      h += (((unsigned long long)a.w << 32) | a.z) * psum_mult(w + 1);
+    }
+  } else if (VEC == 8) {
+    const uint2 a = *reinterpret_cast<const uint2*>(flat);
+    const uint2 p0 = widen_pair(a.x, code), p1 = widen_pair(a.y, code);
+    *reinterpret_cast<uint4*>(dst) = make_uint4(p0.x, p0.y, p1.x, p1.y);
+    if (HASH) {
+      h += (((unsigned long long)a.y << 32) | a.x) * psum_mult(file_off >> 3);
+    }
+  } else if (VEC == 4) {
+    const uint32_t a = *reinterpret_cast<const uint32_t*>(flat);
+    *reinterpret_cast<uint2*>(dst) = widen_pair(a, code);
+    if (HASH) {
+      h += ((unsigned long long)a << (8 * (file_off & 7))) *
+           psum_mult(file_off >> 3);
+    }
+  } else {
+    const uint32_t a = *reinterpret_cast<const uint16_t*>(flat);
+    *reinterpret_cast<uint32_t*>(dst) =
+        code == kCastBF16toF32 ? bf16_to_f32_bits(a) : f16_to_f32_bits(a);
+    if (HASH) {
+      h += ((unsigned long long)a << (8 * (file_off & 7))) *
+           psum_mult(file_off >> 3);
+    }
+  }
+  return h;
+}
+
+// Widen counterpart of process_range_cast, direction reversed: [s, e) and
+// every index below are in stored (flat-side) bytes; the f32 target sits
+// at twice the offset, computed in 64 bits.
+template <int VEC, bool HASH>
+__device__ unsigned long long process_range_widen(const Desc& d,
+                                                  const char* flat_base,
+                                                  uint32_t s, uint32_t e,
+                                                  unsigned long long hash_off) {
+  const char* flat = flat_base + d.flat_off;
+  char* base = const_cast<char*>(d.tensor_base);
+  const uint32_t tid = threadIdx.x;
+  const uint32_t rb = d.row_bytes;
+  const uint32_t code = d.cast;
+  unsigned long long h = 0;
+  if (d.ndim == 0 || rb == d.nbytes) {
+    for (uint32_t i = s + tid * VEC; i < e; i += kBlockThreads * VEC) {
+      h += widen_vec<VEC, HASH>(base + 2ull * i, flat + i, code, hash_off + i);
+    }
+    return h;
+  }
+  if (rb >= kWideRowBytes) {
+    // wide rows: rows sequential, lanes across columns
+    uint32_t row = s / rb;
+    uint32_t col = s - row * rb;
+    uint32_t off = s;
+    while (off < e) {
+      char* dst = base + row_offset(d, row) + 2ull * col;
+      uint32_t n = min(rb - col, e - off);
+      for (uint32_t i = tid * VEC; i < n; i += kBlockThreads * VEC) {
+        h += widen_vec<VEC, HASH>(dst + 2ull * i, flat + off + i, code,
+                                  hash_off + off + i);
+      }
+      off += n;
+      ++row;
+      col = 0;
+    }
+  } else {
+    // narrow rows: one lane per row; flat-side reads stay coalesced
+    uint32_t first_row = s / rb;
+    uint32_t last_row = (e - 1) / rb;
+    for (uint32_t r = first_row + tid; r <= last_row; r += kBlockThreads) {
+      char* dst = base + row_offset(d, r);
+      uint32_t flat_pos = r * rb;
+      uint32_t lo = flat_pos < s ? (s - flat_pos) : 0;
+      uint32_t hi = (flat_pos + rb > e) ? (e - flat_pos) : rb;
+      for (uint32_t i = lo; i < hi; i += VEC) {
+        h += widen_vec<VEC, HASH>(dst + 2ull * i, flat + flat_pos + i, code,
+                                  hash_off + flat_pos + i);
+      }
+    }
+  }
+  return h;
+}
+
+// Restore kernel: scatter (and, when WIDEN, widen) flat bytes into strided
+// device tensors; when HASH, hash_out[i] accumulates the psum64 of
+// descriptor i's flat bytes at file offset hash_byte0 + flat_off. A kernel
+// of its own rather than more pack_kernel instantiations: the extra
+// argument would otherwise change every gather kernel's signature. The
+// host caps nbytes at 2^32 - 64 KiB so no u32 index below can wrap.
+template <bool HASH, bool WIDEN>
+__global__ __launch_bounds__(kBlockThreads) void unpack_kernel(
+    const Desc* __restrict__ descs, int n,
+    const unsigned long long* __restrict__ wu_prefix,
+    unsigned long long total_wus, const char* __restrict__ flat_base,
+    unsigned long long* __restrict__ hash_out,
+    unsigned long long hash_byte0) {
+  for (unsigned long long wu = blockIdx.x; wu < total_wus; wu += gridDim.x) {
+    // binary search: which tensor owns this work unit
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+      int mid = (lo + hi + 1) >> 1;
+      if (wu_prefix[mid] <= wu) lo = mid;
+      else hi = mid - 1;
+    }
+    const Desc d = descs[lo];
+    unsigned long long local_wu = wu - wu_prefix[lo];
+    uint32_t s = (uint32_t)(local_wu * kWorkUnitBytes);
+    uint32_t e = d.nbytes - s > kWorkUnitBytes ? s + kWorkUnitBytes : d.nbytes;
+    const unsigned long long ho = hash_byte0 + d.flat_off;
+    char* fb = const_cast<char*>(flat_base);
+    unsigned long long h = 0;
+    if (WIDEN && d.cast != kCastNone) {
+      switch (d.vec) {
+        case 16: h = process_range_widen<16, HASH>(d, fb, s, e, ho); break;
+        case 8: h = process_range_widen<8, HASH>(d, fb, s, e, ho); break;
+        case 4: h = process_range_widen<4, HASH>(d, fb, s, e, ho); break;
+        default: h = process_range_widen<2, HASH>(d, fb, s, e, ho); break;
+      }
+    } else {
+      switch (d.vec) {
+        case 16: h = process_range<16, false, HASH>(d, fb, s, e, ho); break;
+        case 8: h = process_range<8, false, HASH>(d, fb, s, e, ho); break;
+        case 4: h = process_range<4, false, HASH>(d, fb, s, e, ho); break;
+        case 2: h = process_range<2, false, HASH>(d, fb, s, e, ho); break;
+        default: h = process_range<1, false, HASH>(d, fb, s, e, ho); break;
+      }
+    }
+    if (HASH) {
+      // wave64 reduction, then one atomic per wave per work unit
+      for (int delta = 32; delta > 0; delta >>= 1) {
+        h += __shfl_down(h, delta, 64);
+      }
+      if ((threadIdx.x & 63) == 0 && h != 0) {
+        atomicAdd(&hash_out[lo], h);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host-side op management
 // ---------------------------------------------------------------------------
 
@@ -488,8 +749,10 @@ void chain_after(hipStream_t side, uintptr_t producer_stream, int device) {
 // flat desc rows from python: 19 u64 each (see ops/staging.py)
 constexpr int kRowInts = 19;
 
+// `widen`: the caller is unpack_h2d, which takes the widening codes (and
+// not the narrowing ones); everything else takes codes 0..2 only.
 std::vector<Desc> parse_descs(const std::vector<unsigned long long>& flat,
-                              int n) {
+                              int n, bool widen = false) {
   if ((int)flat.size() != n * kRowInts) {
     throw std::runtime_error("bad descriptor array length");
   }
@@ -514,12 +777,21 @@ std::vector<Desc> parse_descs(const std::vector<unsigned long long>& flat,
     if (d.ndim > (uint32_t)kMaxDims) {
       throw std::runtime_error("too many outer dims");
     }
-    if (r[18] > kCastF16) {
+    if (r[18] > kCastF16toF32) {
       throw std::runtime_error("unknown cast code in descriptor");
+    }
+    if (!widen && r[18] > kCastF16) {
+      throw std::runtime_error(
+          "widening cast descriptors are scatter-only (unpack_h2d)");
+    }
+    if (widen && r[18] != kCastNone && r[18] <= kCastF16) {
+      throw std::runtime_error(
+          "unpack_h2d does not support narrowing cast descriptors");
     }
     d.cast = (uint32_t)r[18];
     if (d.cast != kCastNone && d.nbytes != 0) {
-      // the cast lanes do vector loads of 2*vec and stores of vec bytes:
+      // the cast lanes move 2*vec bytes on the tensor side and vec bytes
+      // on the flat side, each as naturally aligned vector accesses:
       // refuse a descriptor whose layout would misalign or overrun them
       const uint32_t v = d.vec;
       if (v != 16 && v != 8 && v != 4 && v != 2) {
@@ -543,22 +815,76 @@ std::vector<Desc> parse_descs(const std::vector<unsigned long long>& flat,
   return descs;
 }
 
+// unpack_h2d's extra checks, all before the GPU is touched: every flat
+// range lies inside the payload, and every vector access the kernel will
+// make on either side is naturally aligned.
+void check_unpack_descs(const std::vector<Desc>& descs, uintptr_t slab_ptr,
+                        uintptr_t pinned_ptr, unsigned long long total_bytes,
+                        unsigned long long hash_byte0) {
+  if (hash_byte0 % 8 != 0) {
+    throw std::runtime_error("unpack_h2d: hash_byte0 must be 8-aligned");
+  }
+  if (slab_ptr % 16 != 0) {
+    throw std::runtime_error("unpack_h2d: slab must be 16-aligned");
+  }
+  for (const Desc& d : descs) {
+    if (d.nbytes == 0) continue;
+    // u32 indices inside the kernel step by at most 4 KiB past nbytes
+    if (d.nbytes > 0xFFFFFFFFu - kWorkUnitBytes) {
+      throw std::runtime_error(
+          "unpack_h2d: tensor too large (>= 4 GiB - 64 KiB stored)");
+    }
+    if (d.flat_off > total_bytes || d.nbytes > total_bytes - d.flat_off) {
+      throw std::runtime_error("unpack_h2d: descriptor outside the payload");
+    }
+    const uint32_t v = d.vec;
+    if (v != 16 && v != 8 && v != 4 && v != 2 && v != 1) {
+      throw std::runtime_error("unpack_h2d: vec must be 16/8/4/2/1");
+    }
+    if (d.row_bytes == 0 || d.row_bytes % v != 0 ||
+        d.nbytes % d.row_bytes != 0) {
+      throw std::runtime_error("unpack_h2d: row_bytes/vec mismatch");
+    }
+    if ((pinned_ptr + d.flat_off) % v != 0) {
+      throw std::runtime_error(
+          "unpack_h2d: flat address not aligned for its vec");
+    }
+    if (d.cast == kCastNone) {
+      // widen descriptors had their tensor side checked by parse_descs
+      bool ok = reinterpret_cast<uintptr_t>(d.tensor_base) % v == 0;
+      for (uint32_t k = 0; k < d.ndim; ++k) {
+        ok = ok && ((unsigned long long)d.strides[k] % v) == 0;
+      }
+      if (!ok) {
+        throw std::runtime_error(
+            "unpack_h2d: tensor not aligned for its vec");
+      }
+    }
+  }
+}
+
 long long launch_pack(const std::vector<unsigned long long>& flat, int n,
                       uintptr_t slab_ptr, uintptr_t pinned_ptr,
                       unsigned long long total_bytes, uintptr_t producer_stream,
-                      int device, bool gather, uintptr_t hash_out_ptr) {
+                      int device, bool gather, uintptr_t hash_out_ptr,
+                      bool unpack = false, unsigned long long hash_byte0 = 0) {
+  // `unpack` (scatter only) selects unpack_kernel: widening descriptors
+  // and the fused psum64 at file offset hash_byte0 + flat_off
+  std::vector<Desc> descs = parse_descs(flat, n, unpack);
+  bool any_cast = false;
+  for (const Desc& d : descs) any_cast = any_cast || d.cast != kCastNone;
+  if (any_cast && !gather && !unpack) {
+    // scatter_h2d stays a plain byte scatter; refuse before touching the GPU
+    throw std::runtime_error(
+        "scatter_h2d does not support cast descriptors (gather only)");
+  }
+  if (unpack) check_unpack_descs(descs, slab_ptr, pinned_ptr, total_bytes,
+                                 hash_byte0);
+
   HIP_CHECK(hipSetDevice(device));
   DeviceCtx& ctx = get_ctx(device);
   hipStream_t stream = gather ? ctx.d2h_stream : ctx.h2d_stream;
 
-  std::vector<Desc> descs = parse_descs(flat, n);
-  bool any_cast = false;
-  for (const Desc& d : descs) any_cast = any_cast || d.cast != kCastNone;
-  if (any_cast && !gather) {
-    // widening on restore stays with torch; refuse before touching the GPU
-    throw std::runtime_error(
-        "scatter_h2d does not support cast descriptors (gather only)");
-  }
   std::vector<unsigned long long> wu_prefix(n + 1, 0);
   for (int i = 0; i < n; ++i) {
     unsigned long long wus =
@@ -609,7 +935,9 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
   // Grid cap. Direct mode is PCIe-bound: 128 workgroups already sustain
   // the measured ~51 GB/s host-link ceiling (grid sweep, profiles/), so a
   // small grid leaves the CUs to overlapped training compute. Slab mode
-  // gathers at HBM speed and wants the chip filled (all 8 XCDs).
+  // gathers at HBM speed and wants the chip filled (all 8 XCDs). The
+  // restore kernel's reads of pinned memory behave the same way: 128-256
+  // workgroups reach the link rate, 1024+ lose a few percent.
   bool direct_mode = (slab_ptr == 0);
   unsigned long long grid_cap = direct_mode ? 256ull : 16384ull;
   if (const char* env = getenv("TSAMD_PACK_GRID")) {
@@ -620,7 +948,17 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
       total_wus == 0 ? 1 : total_wus, grid_cap);
   unsigned long long* hash_out =
       reinterpret_cast<unsigned long long*>(hash_out_ptr);
-  if (any_cast && hash_out != nullptr) {
+  if (unpack) {
+    const bool hash = hash_out != nullptr;
+    auto kernel = any_cast ? (hash ? unpack_kernel<true, true>
+                                   : unpack_kernel<false, true>)
+                           : (hash ? unpack_kernel<true, false>
+                                   : unpack_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
+                       d_descs, n, d_prefix, total_wus,
+                       static_cast<const char*>(flat_base), hash_out,
+                       hash_byte0);
+  } else if (any_cast && hash_out != nullptr) {
     hipLaunchKernelGGL((pack_kernel<true, true, true>), dim3(grid),
                        dim3(kBlockThreads), 0, stream, d_descs, n, d_prefix,
                        total_wus, flat_base, hash_out);
@@ -708,6 +1046,17 @@ static long long scatter_h2d(const std::vector<unsigned long long>& flat, int n,
                              uintptr_t producer_stream, int device) {
   return launch_pack(flat, n, slab_ptr, pinned_ptr, total_bytes,
                      producer_stream, device, /*gather=*/false, 0);
+}
+
+static long long unpack_h2d(const std::vector<unsigned long long>& flat,
+                            int n, uintptr_t slab_ptr, uintptr_t pinned_ptr,
+                            unsigned long long total_bytes,
+                            uintptr_t producer_stream, int device,
+                            uintptr_t hash_out_ptr = 0,
+                            unsigned long long hash_byte0 = 0) {
+  return launch_pack(flat, n, slab_ptr, pinned_ptr, total_bytes,
+                     producer_stream, device, /*gather=*/false, hash_out_ptr,
+                     /*unpack=*/true, hash_byte0);
 }
 
 // ---------------------------------------------------------------------------
@@ -977,6 +1326,15 @@ PYBIND11_MODULE(_csnap, m) {
         py::arg("hash_out_ptr") = 0);
   m.def("scatter_h2d", &scatter_h2d,
         "copy pinned host bytes to device and scatter into strided tensors");
+  m.def("unpack_h2d", &unpack_h2d,
+        "restore scatter: pinned host bytes (read in place, or through a "
+        "device slab when slab_ptr != 0) into strided tensors, widening "
+        "bf16/f16 -> f32 per descriptor; hash_out_ptr != 0 also accumulates "
+        "each descriptor's psum64 at file offset hash_byte0 + flat_off",
+        py::arg("flat"), py::arg("n"), py::arg("slab_ptr"),
+        py::arg("pinned_ptr"), py::arg("total_bytes"),
+        py::arg("producer_stream"), py::arg("device"),
+        py::arg("hash_out_ptr") = 0, py::arg("hash_byte0") = 0);
   m.def("psum64_host", &psum64_host,
         "single-pass threaded host psum64 of a buffer",
         py::arg("buf"), py::arg("word_base") = 0);

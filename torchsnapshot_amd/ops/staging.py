@@ -126,6 +126,31 @@ def cast_code(src: torch.dtype, dst: Optional[torch.dtype]) -> int:
     return code
 
 
+# widening on restore (scatter only): the descriptor convention is the cast
+# one, flat side in stored 2-byte units and tensor side in float32 bytes
+CAST_BF16_TO_F32 = 3
+CAST_F16_TO_F32 = 4
+
+_WIDEN_CODES = {
+    (torch.bfloat16, torch.float32): CAST_BF16_TO_F32,
+    (torch.float16, torch.float32): CAST_F16_TO_F32,
+}
+
+
+def widen_code(stored: torch.dtype, target: torch.dtype) -> int:
+    """Descriptor cast code for restoring ``stored``-typed bytes into a
+    ``target``-typed tensor. An unsupported pair raises."""
+    if stored == target:
+        return CAST_NONE
+    code = _WIDEN_CODES.get((stored, target))
+    if code is None:
+        raise ValueError(
+            f"the scatter kernel cannot restore {stored} into {target}; "
+            "supported: equal dtypes, bfloat16 -> float32, float16 -> float32"
+        )
+    return code
+
+
 def build_pack_items(
     tensors: Sequence[torch.Tensor],
     out_dtypes: Optional[Sequence[Optional[torch.dtype]]] = None,
@@ -227,6 +252,104 @@ def _build_cast_item(
         vec=vec,
         cast=cast,
     )
+
+
+def build_scatter_items(
+    targets: Sequence[torch.Tensor],
+    stored_dtypes: Sequence[torch.dtype],
+    flat_offsets: Sequence[int],
+    flat_base: int = 0,
+) -> List[PackItem]:
+    """Descriptors for scattering payload bytes into ``targets`` (restore).
+
+    Unlike a gather, the flat side is not laid out here: member ``i`` sits
+    at ``flat_offsets[i]`` (its byte_range within the read), and the flat
+    buffer starts at address ``flat_base``. ``vec`` therefore has to divide
+    the flat address as well as everything build_pack_items makes it
+    divide. A bf16/f16 payload for a float32 target becomes a widen item."""
+    items: List[PackItem] = []
+    for t, stored, off in zip(targets, stored_dtypes, flat_offsets):
+        code = widen_code(stored, t.dtype)
+        if code != CAST_NONE:
+            it = _build_cast_item(t, stored, code, off)
+        else:
+            it = build_pack_items([t])[0][0]
+            it.flat_offset = off
+        if it.nbytes:
+            it.vec = math.gcd(it.vec, flat_base + off)
+            if it.cast != CAST_NONE and it.vec < 2:
+                raise ValueError(
+                    f"cannot widen from a payload at odd address "
+                    f"{flat_base + off:#x}"
+                )
+        items.append(it)
+    return items
+
+
+# u32 indices inside the scatter kernel step up to 4 KiB past a tensor's
+# stored size; the extension refuses anything closer to 4 GiB than this
+_SCATTER_MAX_STORED_BYTES = 2**32 - 2**16
+
+
+def scatter_plan(
+    target: torch.Tensor, stored_dtype: torch.dtype
+) -> Optional[int]:
+    """The descriptor cast code with which the scatter kernel can restore a
+    ``stored_dtype`` payload into ``target``, or None when it must not be
+    used and the caller keeps the torch path."""
+    if target.device.type != "cuda":
+        return None
+    return _scatter_layout_plan(target, stored_dtype)
+
+
+def _scatter_layout_plan(
+    target: torch.Tensor, stored_dtype: torch.dtype
+) -> Optional[int]:
+    """scatter_plan() past the device check."""
+    if (
+        target.layout != torch.strided
+        or target.is_quantized
+        or target.is_conj()
+        or target.is_neg()
+    ):
+        return None
+    if stored_dtype != target.dtype and (
+        (stored_dtype, target.dtype) not in _WIDEN_CODES
+    ):
+        return None
+    # overlapping elements: the kernel writes them in no defined order
+    if any(st == 0 and sz > 1 for sz, st in zip(target.shape, target.stride())):
+        return None
+    if torch._debug_has_internal_overlap(target) != 0:
+        return None
+    sizes, strides = collapse_layout(target)
+    n_outer = len(sizes) - 1 if strides[-1] == 1 else len(sizes)
+    if n_outer > 6:
+        return None
+    if target.numel() * stored_dtype.itemsize >= _SCATTER_MAX_STORED_BYTES:
+        return None
+    # torch strides are whole elements, so the base address decides whether
+    # every element is aligned
+    if target.data_ptr() % target.element_size():
+        return None
+    return widen_code(stored_dtype, target.dtype)
+
+
+def scatter_member(
+    target: torch.Tensor, stored_dtype: torch.dtype, flat_offset: int
+) -> Optional[Tuple[torch.Tensor, torch.dtype, int]]:
+    """One StagingEngine.scatter member, or None when this restore has to
+    stay on the torch path: TSAMD_RESTORE_MODE=torch, no extension, an
+    ineligible target, or a payload offset that splits an element."""
+    if (
+        knobs.get_restore_mode() == "torch"
+        or not HIP_EXT_AVAILABLE
+        or knobs.is_hip_staging_disabled()
+        or flat_offset % stored_dtype.itemsize
+        or scatter_plan(target, stored_dtype) is None
+    ):
+        return None
+    return (target, stored_dtype, flat_offset)
 
 
 def _items_to_flat(items: List[PackItem]) -> List[int]:
@@ -599,6 +722,71 @@ class StagingEngine:
                 batch._device_slab = slab
             batch._handle = handle
 
+    # -- restore ------------------------------------------------------------
+
+    def scatter(
+        self,
+        pinned_block: PinnedBlock,
+        nbytes: int,
+        members: Sequence[Tuple[torch.Tensor, torch.dtype, int]],
+        expected_psum: Optional[Tuple[int, int]] = None,
+        what: str = "payload",
+    ) -> None:
+        """Restore the first ``nbytes`` of ``pinned_block`` into device
+        tensors with ONE scatter-kernel launch. ``members`` holds
+        ``(target, stored_dtype, flat_offset)`` triples, each eligible per
+        scatter_plan(); bf16/f16 payloads widen into float32 targets inside
+        the kernel. Returns once the targets hold the bytes, so the caller
+        may release the block.
+
+        ``expected_psum=(value, word_base)``: the kernel also accumulates
+        the psum64 of every member's payload bytes, at file offset
+        ``word_base * 8`` for the block's first byte, and their sum is
+        checked against ``value``. The targets have already been written
+        when the mismatch is raised."""
+        if not self._use_ext:
+            _require_ext()
+            raise RuntimeError("scatter() needs the HIP staging extension")
+        members = [m for m in members if m[0].numel() > 0]
+        if not members:
+            if expected_psum is not None and expected_psum[0] != 0:
+                _raise_psum_mismatch(what, expected_psum[0], 0)
+            return
+        dev_index = self.device.index or 0
+        base = pinned_block.tensor.data_ptr()
+        items = build_scatter_items(
+            [m[0] for m in members],
+            [m[1] for m in members],
+            [m[2] for m in members],
+            flat_base=base,
+        )
+        with torch.cuda.device(dev_index):
+            cur_stream = torch.cuda.current_stream().cuda_stream
+            slab = None
+            if knobs.get_restore_mode() == "slab":
+                slab = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            hash_t = None
+            if expected_psum is not None:
+                hash_t = torch.zeros(
+                    len(items), dtype=torch.uint64, device=self.device
+                )
+            handle = _csnap.unpack_h2d(
+                _items_to_flat(items),
+                len(items),
+                slab.data_ptr() if slab is not None else 0,
+                base,
+                nbytes,
+                cur_stream,
+                dev_index,
+                hash_t.data_ptr() if hash_t is not None else 0,
+                expected_psum[1] * 8 if expected_psum is not None else 0,
+            )
+            _csnap.wait(handle)
+            if hash_t is not None:
+                got = sum(int(v) for v in hash_t.cpu().tolist()) % (1 << 64)
+                if got != expected_psum[0]:
+                    _raise_psum_mismatch(what, expected_psum[0], got)
+
     # -- debug fallback -----------------------------------------------------
 
     def _stage_torch_fallback(
@@ -689,12 +877,16 @@ def verify_device_psum(
     value, word_base = expected
     got = device_psum64(dev_u8, word_base * 8)
     if got != value:
-        raise RuntimeError(
-            f"checksum mismatch for '{what}': snapshot recorded "
-            f"psum64:{value:016x}, device read back psum64:{got:016x} — "
-            "the file is corrupted or was modified after the snapshot "
-            "was committed"
-        )
+        _raise_psum_mismatch(what, value, got)
+
+
+def _raise_psum_mismatch(what: str, value: int, got: int) -> None:
+    raise RuntimeError(
+        f"checksum mismatch for '{what}': snapshot recorded "
+        f"psum64:{value:016x}, device read back psum64:{got:016x} — "
+        "the file is corrupted or was modified after the snapshot "
+        "was committed"
+    )
 
 
 _engines: Dict[int, StagingEngine] = {}
