@@ -40,7 +40,11 @@ for step in range(1, 31):
         if pending is not None:
             pending.wait()  # a no-op if storage I/O already drained
         t0 = time.monotonic()
-        pending = Snapshot.async_take(f"{ckpt_root}/step_{step}", app_state)
+        # nonfinite="error": a diverged state (NaN/Inf) raises here instead
+        # of being written over a good checkpoint
+        pending = Snapshot.async_take(
+            f"{ckpt_root}/step_{step}", app_state, nonfinite="error"
+        )
         print(
             f"step {step}: checkpoint staged in "
             f"{time.monotonic() - t0:.3f}s (training continues)"

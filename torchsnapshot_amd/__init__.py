@@ -8,6 +8,7 @@ budget; metadata coordination runs over RCCL (torch.distributed "nccl"
 backend on ROCm) or gloo.
 """
 
+from .nonfinite import NonFiniteStateError, find_nonfinite
 from .rng_state import RNGState
 from .snapshot import PendingSnapshot, Snapshot
 from .state_dict import StateDict
@@ -21,5 +22,7 @@ __all__ = [
     "AppState",
     "StateDict",
     "RNGState",
+    "NonFiniteStateError",
+    "find_nonfinite",
     "__version__",
 ]

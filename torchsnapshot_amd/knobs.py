@@ -134,6 +134,20 @@ def get_restore_mode() -> str:
     return mode
 
 
+def get_nonfinite_policy() -> str:
+    """What take()/async_take() do about NaN or Inf in the state when their
+    ``nonfinite`` argument is None. "ignore" (default): nothing runs.
+    "warn": scan before the snapshot path is touched and log the offending
+    leaves. "error": scan and raise NonFiniteStateError instead of saving,
+    leaving an earlier snapshot at the path intact."""
+    policy = os.environ.get("TSAMD_NONFINITE", "ignore")
+    if policy not in ("ignore", "warn", "error"):
+        raise ValueError(
+            f"TSAMD_NONFINITE must be ignore|warn|error, got {policy}"
+        )
+    return policy
+
+
 def get_async_shadow_mode() -> str:
     """Shadow-clone async snapshots: "auto" (default) clones device
     tensors at HBM rate before async_take returns, when free HBM allows —

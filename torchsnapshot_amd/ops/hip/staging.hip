@@ -11,6 +11,8 @@
 //     the same launch (save_dtype), so only stored-size bytes leave the GPU
 //   - scatter kernel (same code path, direction-reversed) for restore, with
 //     bf16/f16 -> f32 widening and the psum64 check fused into the launch
+//   - scan kernel: NaN / Inf counts per tensor over the same descriptors,
+//     read-only, one launch for the whole state (the nonfinite= policy)
 //   - SDMA copies (hipMemcpyAsync) slab <-> pinned host memory; the slab
 //     can also be skipped entirely ("direct" mode): the kernel writes
 //     gathered bytes straight into pinned host memory over PCIe
@@ -682,6 +684,232 @@ __global__ __launch_bounds__(kBlockThreads) void unpack_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// non-finite scan: count NaN and +-Inf elements per descriptor, read-only.
+// Same descriptors, work units and traversals as the gather; there is no
+// flat side (flat_off is unused) and nbytes/row_bytes/vec are the tensor's
+// own bytes. The element class travels in an array beside the descriptors,
+// so Desc::cast stays what parse_descs polices for gather and scatter.
+// Classification is integer arithmetic on the loaded words, like the casts:
+// no dependence on the wave's float mode. The two "stored" classes count
+// what the save_dtype narrowing above will write: a finite f32 at or above
+// 65520 (0x477FF000) rounds to f16 inf, one at or above 0x7F7F8000 to bf16
+// inf.
+// ---------------------------------------------------------------------------
+
+constexpr uint32_t kScanF64 = 0;
+constexpr uint32_t kScanF32 = 1;
+constexpr uint32_t kScanF16 = 2;
+constexpr uint32_t kScanBF16 = 3;
+constexpr uint32_t kScanE5M2 = 4;
+constexpr uint32_t kScanE4M3FN = 5;
+constexpr uint32_t kScanFNUZ = 6;  // e4m3fnuz and e5m2fnuz: NaN is 0x80
+constexpr uint32_t kScanF32asF16 = 7;
+constexpr uint32_t kScanF32asBF16 = 8;
+constexpr uint32_t kScanClasses = 9;
+
+__device__ __host__ constexpr uint32_t scan_elem_size(uint32_t cls) {
+  return cls == kScanF64 ? 8u
+         : (cls == kScanF32 || cls >= kScanF32asF16) ? 4u
+         : (cls == kScanF16 || cls == kScanBF16) ? 2u
+                                                 : 1u;
+}
+
+// Classify the elements packed in one 32-bit word. A narrower load arrives
+// zero-extended, and an all-zero element is finite in every class, so the
+// padding never counts. The 8- and 16-bit classes test all elements of the
+// word at once: with the sign bits cleared every element is at most
+// 0x7F / 0x7FFF, so adding (limit's complement) carries into the element's
+// own top bit exactly when it exceeds the limit, and never into a
+// neighbour.
+template <uint32_t CLS>
+__device__ inline void scan_word(uint32_t w, uint32_t& nan, uint32_t& inf) {
+  if (CLS == kScanF32 || CLS == kScanF32asF16 || CLS == kScanF32asBF16) {
+    const uint32_t a = w & 0x7FFFFFFFu;
+    const uint32_t first_inf = CLS == kScanF32asF16    ? 0x477FF000u
+                               : CLS == kScanF32asBF16 ? 0x7F7F8000u
+                                                       : 0x7F800000u;
+    nan += a > 0x7F800000u;
+    inf += (a >= first_inf) & (a <= 0x7F800000u);
+  } else if (CLS == kScanF16 || CLS == kScanBF16) {
+    const uint32_t a = w & 0x7FFF7FFFu;
+    const uint32_t gt = CLS == kScanF16 ? 0x03FF03FFu : 0x007F007Fu;
+    const uint32_t ge = CLS == kScanF16 ? 0x04000400u : 0x00800080u;
+    const uint32_t n = __popc((a + gt) & 0x80008000u);
+    nan += n;
+    inf += __popc((a + ge) & 0x80008000u) - n;
+  } else if (CLS == kScanE5M2) {
+    const uint32_t a = w & 0x7F7F7F7Fu;
+    const uint32_t n = __popc((a + 0x03030303u) & 0x80808080u);
+    nan += n;
+    inf += __popc((a + 0x04040404u) & 0x80808080u) - n;
+  } else if (CLS == kScanE4M3FN) {
+    const uint32_t a = w & 0x7F7F7F7Fu;
+    nan += __popc((a + 0x01010101u) & 0x80808080u);
+  } else {  // kScanFNUZ: the whole byte equals 0x80
+    const uint32_t x = w ^ 0x80808080u;
+    // exact zero-byte test: top bit set where the byte of x is zero
+    const uint32_t z =
+        ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
+    nan += __popc(z);
+  }
+}
+
+__device__ inline void scan_f64(uint32_t lo, uint32_t hi, uint32_t& nan,
+                                uint32_t& inf) {
+  const unsigned long long a =
+      (((unsigned long long)hi << 32) | lo) & 0x7FFFFFFFFFFFFFFFull;
+  nan += a > 0x7FF0000000000000ull;
+  inf += a == 0x7FF0000000000000ull;
+}
+
+// One naturally aligned VEC-byte load (VEC >= the element size) and the
+// classification of every element in it.
+template <int VEC, uint32_t CLS>
+__device__ inline void scan_vec(const char* p, uint32_t& nan, uint32_t& inf) {
+  if (VEC == 16) {
+    const uint4 a = *reinterpret_cast<const uint4*>(p);
+    if (CLS == kScanF64) {
+      scan_f64(a.x, a.y, nan, inf);
+      scan_f64(a.z, a.w, nan, inf);
+    } else {
+      scan_word<CLS>(a.x, nan, inf);
+      scan_word<CLS>(a.y, nan, inf);
+      scan_word<CLS>(a.z, nan, inf);
+      scan_word<CLS>(a.w, nan, inf);
+    }
+  } else if (VEC == 8) {
+    const uint2 a = *reinterpret_cast<const uint2*>(p);
+    if (CLS == kScanF64) {
+      scan_f64(a.x, a.y, nan, inf);
+    } else {
+      scan_word<CLS>(a.x, nan, inf);
+      scan_word<CLS>(a.y, nan, inf);
+    }
+  } else if (CLS != kScanF64) {
+    uint32_t w;
+    if (VEC == 4) w = *reinterpret_cast<const uint32_t*>(p);
+    else if (VEC == 2) w = *reinterpret_cast<const uint16_t*>(p);
+    else w = *reinterpret_cast<const unsigned char*>(p);
+    scan_word<CLS>(w, nan, inf);
+  }
+}
+
+// Scan counterpart of process_range: [s, e) of the tensor's own bytes for
+// one work unit, the same three traversals, loads only.
+template <int VEC, uint32_t CLS>
+__device__ __forceinline__ void scan_range(const Desc& d, uint32_t s,
+                                           uint32_t e, uint32_t& nan,
+                                           uint32_t& inf) {
+  const uint32_t tid = threadIdx.x;
+  const uint32_t rb = d.row_bytes;
+  if (d.ndim == 0 || rb == d.nbytes) {
+    const char* src = d.tensor_base;
+#pragma unroll 4
+    for (uint32_t i = s + tid * VEC; i < e; i += kBlockThreads * VEC) {
+      scan_vec<VEC, CLS>(src + i, nan, inf);
+    }
+    return;
+  }
+  if (rb >= kWideRowBytes) {
+    // wide rows: rows sequential, lanes across columns
+    uint32_t row = s / rb;
+    uint32_t col = s - row * rb;
+    uint32_t off = s;
+    while (off < e) {
+      const char* src = d.tensor_base + row_offset(d, row) + col;
+      uint32_t n = min(rb - col, e - off);
+      for (uint32_t i = tid * VEC; i < n; i += kBlockThreads * VEC) {
+        scan_vec<VEC, CLS>(src + i, nan, inf);
+      }
+      off += n;
+      ++row;
+      col = 0;
+    }
+  } else {
+    // narrow rows: one lane per row
+    uint32_t first_row = s / rb;
+    uint32_t last_row = (e - 1) / rb;
+    for (uint32_t r = first_row + tid; r <= last_row; r += kBlockThreads) {
+      const char* src = d.tensor_base + row_offset(d, r);
+      uint32_t flat_pos = r * rb;
+      uint32_t lo = flat_pos < s ? (s - flat_pos) : 0;
+      uint32_t hi = (flat_pos + rb > e) ? (e - flat_pos) : rb;
+      for (uint32_t i = lo; i < hi; i += VEC) {
+        scan_vec<VEC, CLS>(src + i, nan, inf);
+      }
+    }
+  }
+}
+
+// The class switch sits outside the traversal: the inner loops are
+// specialised per (vec, class) and never branch per element. The host
+// refuses vec below the element size, so those pairs are not instantiated.
+template <uint32_t CLS>
+__device__ __forceinline__ void scan_class(const Desc& d, uint32_t s,
+                                           uint32_t e, uint32_t& nan,
+                                           uint32_t& inf) {
+  constexpr uint32_t ESZ = scan_elem_size(CLS);
+  switch (d.vec) {
+    case 16: scan_range<16, CLS>(d, s, e, nan, inf); break;
+    case 8: scan_range<8, CLS>(d, s, e, nan, inf); break;
+    case 4:
+      if constexpr (ESZ <= 4) scan_range<4, CLS>(d, s, e, nan, inf);
+      break;
+    case 2:
+      if constexpr (ESZ <= 2) scan_range<2, CLS>(d, s, e, nan, inf);
+      break;
+    default:
+      if constexpr (ESZ <= 1) scan_range<1, CLS>(d, s, e, nan, inf);
+      break;
+  }
+}
+
+// counts[2*i] / counts[2*i+1]: NaN / Inf elements of descriptor i. A work
+// unit holds at most 64 Ki elements, so the per-lane and per-wave counters
+// fit u32; the totals are u64.
+__global__ __launch_bounds__(kBlockThreads) void scan_kernel(
+    const Desc* __restrict__ descs, const uint32_t* __restrict__ classes,
+    int n, const unsigned long long* __restrict__ wu_prefix,
+    unsigned long long total_wus, unsigned long long* __restrict__ counts) {
+  for (unsigned long long wu = blockIdx.x; wu < total_wus; wu += gridDim.x) {
+    // binary search: which tensor owns this work unit
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+      int mid = (lo + hi + 1) >> 1;
+      if (wu_prefix[mid] <= wu) lo = mid;
+      else hi = mid - 1;
+    }
+    const Desc d = descs[lo];
+    unsigned long long local_wu = wu - wu_prefix[lo];
+    uint32_t s = (uint32_t)(local_wu * kWorkUnitBytes);
+    uint32_t e = d.nbytes - s > kWorkUnitBytes ? s + kWorkUnitBytes : d.nbytes;
+    uint32_t nan = 0, inf = 0;
+    switch (classes[lo]) {
+      case kScanF64: scan_class<kScanF64>(d, s, e, nan, inf); break;
+      case kScanF32: scan_class<kScanF32>(d, s, e, nan, inf); break;
+      case kScanF16: scan_class<kScanF16>(d, s, e, nan, inf); break;
+      case kScanBF16: scan_class<kScanBF16>(d, s, e, nan, inf); break;
+      case kScanE5M2: scan_class<kScanE5M2>(d, s, e, nan, inf); break;
+      case kScanE4M3FN: scan_class<kScanE4M3FN>(d, s, e, nan, inf); break;
+      case kScanFNUZ: scan_class<kScanFNUZ>(d, s, e, nan, inf); break;
+      case kScanF32asF16:
+        scan_class<kScanF32asF16>(d, s, e, nan, inf);
+        break;
+      default: scan_class<kScanF32asBF16>(d, s, e, nan, inf); break;
+    }
+    // wave64 reduction, then one atomic per wave per work unit and counter
+    for (int delta = 32; delta > 0; delta >>= 1) {
+      nan += __shfl_down(nan, delta, 64);
+      inf += __shfl_down(inf, delta, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      if (nan != 0) atomicAdd(&counts[2 * lo], (unsigned long long)nan);
+      if (inf != 0) atomicAdd(&counts[2 * lo + 1], (unsigned long long)inf);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host-side op management
 // ---------------------------------------------------------------------------
 
@@ -1143,6 +1371,149 @@ static unsigned long long psum64_dev(uintptr_t ptr, unsigned long long nbytes,
   return host_out;
 }
 
+// ---------------------------------------------------------------------------
+// non-finite scan of N strided device tensors in one launch (blocking).
+// `flat` holds gather-style descriptor rows (cast 0, flat_off ignored),
+// `classes` one kScan* code per descriptor. Returns 2*n counts: NaN then
+// Inf elements of each descriptor.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// All before the GPU is touched: every vector load the kernel will make is
+// naturally aligned, covers whole elements and stays inside the rows the
+// descriptor names, and no u32 index can wrap.
+void check_scan_descs(const std::vector<Desc>& descs,
+                      const std::vector<uint32_t>& classes) {
+  if (classes.size() != descs.size()) {
+    throw std::runtime_error("scan_nonfinite: one class code per descriptor");
+  }
+  for (size_t i = 0; i < descs.size(); ++i) {
+    const Desc& d = descs[i];
+    if (classes[i] >= kScanClasses) {
+      throw std::runtime_error("scan_nonfinite: unknown element class");
+    }
+    if (d.cast != kCastNone) {
+      throw std::runtime_error("scan_nonfinite: cast descriptors not allowed");
+    }
+    if (d.nbytes == 0) continue;
+    // u32 indices inside the kernel step by at most 4 KiB past nbytes;
+    // 2^32 - 64 KiB itself is allowed (ops/staging.py's _SCAN_MAX_BYTES)
+    if (d.nbytes > 0xFFFFFFFFu - kWorkUnitBytes + 1u) {
+      throw std::runtime_error(
+          "scan_nonfinite: tensor too large (> 4 GiB - 64 KiB)");
+    }
+    const uint32_t v = d.vec;
+    if (v != 16 && v != 8 && v != 4 && v != 2 && v != 1) {
+      throw std::runtime_error("scan_nonfinite: vec must be 16/8/4/2/1");
+    }
+    if (v < scan_elem_size(classes[i])) {
+      throw std::runtime_error("scan_nonfinite: vec below the element size");
+    }
+    if (d.row_bytes == 0 || d.row_bytes % v != 0 ||
+        d.nbytes % d.row_bytes != 0) {
+      throw std::runtime_error("scan_nonfinite: row_bytes/vec mismatch");
+    }
+    bool ok = reinterpret_cast<uintptr_t>(d.tensor_base) % v == 0;
+    unsigned long long rows = 1;
+    for (uint32_t k = 0; k < d.ndim; ++k) {
+      ok = ok && ((unsigned long long)d.strides[k] % v) == 0;
+      ok = ok && d.strides[k] >= 0 && d.sizes[k] != 0;
+      rows *= d.sizes[k];
+    }
+    if (!ok) {
+      throw std::runtime_error(
+          "scan_nonfinite: tensor not aligned for its vec");
+    }
+    if (d.ndim != 0 && rows * d.row_bytes != d.nbytes) {
+      throw std::runtime_error("scan_nonfinite: sizes do not cover nbytes");
+    }
+  }
+}
+
+}  // namespace
+
+static std::vector<unsigned long long> scan_nonfinite(
+    const std::vector<unsigned long long>& flat,
+    const std::vector<uint32_t>& classes, int n, uintptr_t producer_stream,
+    int device) {
+  std::vector<Desc> descs = parse_descs(flat, n);
+  check_scan_descs(descs, classes);
+  std::vector<unsigned long long> counts(2 * (size_t)n, 0);
+
+  std::vector<unsigned long long> wu_prefix(n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    unsigned long long wus =
+        (descs[i].nbytes + kWorkUnitBytes - 1) / kWorkUnitBytes;
+    wu_prefix[i + 1] = wu_prefix[i] + wus;
+  }
+  const unsigned long long total_wus = wu_prefix[n];
+  if (total_wus == 0) return counts;
+
+  // one device allocation: counters | descriptors | prefix sums | classes
+  const size_t count_bytes = sizeof(unsigned long long) * 2 * n;
+  const size_t desc_bytes = sizeof(Desc) * n;
+  const size_t prefix_bytes = sizeof(unsigned long long) * (n + 1);
+  const size_t class_bytes = sizeof(uint32_t) * n;
+  static_assert(sizeof(Desc) % 8 == 0, "prefix sums must stay 8-aligned");
+  std::vector<char> staging(desc_bytes + prefix_bytes + class_bytes);
+  memcpy(staging.data(), descs.data(), desc_bytes);
+  memcpy(staging.data() + desc_bytes, wu_prefix.data(), prefix_bytes);
+  memcpy(staging.data() + desc_bytes + prefix_bytes, classes.data(),
+         class_bytes);
+
+  // HBM-bound read: fill the chip like the slab-mode gather does
+  unsigned long long grid_cap = 16384ull;
+  if (const char* env = getenv("TSAMD_PACK_GRID")) {
+    long v = atol(env);
+    if (v > 0) grid_cap = (unsigned long long)v;
+  }
+  const unsigned int grid =
+      (unsigned int)std::min<unsigned long long>(total_wus, grid_cap);
+
+  py::gil_scoped_release release;
+  HIP_CHECK(hipSetDevice(device));
+  DeviceCtx& ctx = get_ctx(device);
+  hipStream_t stream = ctx.d2h_stream;
+  chain_after(stream, producer_stream, device);
+
+  void* scratch = nullptr;
+  HIP_CHECK(hipMallocAsync(&scratch, count_bytes + staging.size(), stream));
+  char* base = reinterpret_cast<char*>(scratch);
+  unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(base);
+  const Desc* d_descs = reinterpret_cast<const Desc*>(base + count_bytes);
+  const unsigned long long* d_prefix =
+      reinterpret_cast<const unsigned long long*>(base + count_bytes +
+                                                  desc_bytes);
+  const uint32_t* d_classes = reinterpret_cast<const uint32_t*>(
+      base + count_bytes + desc_bytes + prefix_bytes);
+
+  // enqueue everything, then synchronise whatever happened: the host
+  // buffers above must outlive the copies that read and write them
+  hipError_t err = hipMemsetAsync(d_counts, 0, count_bytes, stream);
+  if (err == hipSuccess) {
+    err = hipMemcpyAsync(base + count_bytes, staging.data(), staging.size(),
+                         hipMemcpyHostToDevice, stream);
+  }
+  if (err == hipSuccess) {
+    hipLaunchKernelGGL(scan_kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
+                       d_descs, d_classes, n, d_prefix, total_wus, d_counts);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess) {
+    err = hipMemcpyAsync(counts.data(), d_counts, count_bytes,
+                         hipMemcpyDeviceToHost, stream);
+  }
+  (void)hipFreeAsync(scratch, stream);
+  const hipError_t sync_err = hipStreamSynchronize(stream);
+  if (err == hipSuccess) err = sync_err;
+  if (err != hipSuccess) {
+    throw std::runtime_error(std::string("scan_nonfinite: ") +
+                             hipGetErrorString(err));
+  }
+  return counts;
+}
+
 // Host-side psum64 (single pass, std::thread-parallel): the
 // python-level vectorized implementations burn ~10 full memory passes
 // on splitmix temporaries (~0.2-0.3 GB/s); this one runs at memcpy-ish
@@ -1341,6 +1712,11 @@ PYBIND11_MODULE(_csnap, m) {
   m.def("psum64_dev", &psum64_dev,
         "psum64 of a flat contiguous device buffer (blocking)",
         py::arg("ptr"), py::arg("nbytes"), py::arg("byte0"),
+        py::arg("producer_stream"), py::arg("device"));
+  m.def("scan_nonfinite", &scan_nonfinite,
+        "count NaN and Inf elements of strided device tensors in one launch "
+        "(blocking); returns [nan_0, inf_0, nan_1, inf_1, ...]",
+        py::arg("flat"), py::arg("classes"), py::arg("n"),
         py::arg("producer_stream"), py::arg("device"));
   m.def("file_write", &file_write,
         "write a buffer to a file (GIL released); reuse=True overwrites an "

@@ -352,6 +352,207 @@ def scatter_member(
     return (target, stored_dtype, flat_offset)
 
 
+# ---------------------------------------------------------------------------
+# non-finite scan descriptors
+# ---------------------------------------------------------------------------
+
+# element classes of the scan kernel (kScan* in ops/hip/staging.hip). The
+# last two count what a save_dtype narrowing of a float32 tensor will write.
+SCAN_F64 = 0
+SCAN_F32 = 1
+SCAN_F16 = 2
+SCAN_BF16 = 3
+SCAN_E5M2 = 4
+SCAN_E4M3FN = 5
+SCAN_FNUZ = 6
+SCAN_F32_AS_F16 = 7
+SCAN_F32_AS_BF16 = 8
+
+_SCAN_CLASSES: Dict[torch.dtype, int] = {
+    torch.float64: SCAN_F64,
+    torch.float32: SCAN_F32,
+    torch.float16: SCAN_F16,
+    torch.bfloat16: SCAN_BF16,
+}
+for _name, _cls in (
+    ("float8_e5m2", SCAN_E5M2),
+    ("float8_e4m3fn", SCAN_E4M3FN),
+    ("float8_e4m3fnuz", SCAN_FNUZ),
+    ("float8_e5m2fnuz", SCAN_FNUZ),
+):
+    if hasattr(torch, _name):
+        _SCAN_CLASSES[getattr(torch, _name)] = _cls
+
+_SCAN_STORED_CLASSES = {
+    CAST_F32_TO_F16: SCAN_F32_AS_F16,
+    CAST_F32_TO_BF16: SCAN_F32_AS_BF16,
+}
+
+# u32 indices inside the scan kernel step up to 4 KiB past a tensor's size;
+# the extension accepts this many bytes and refuses anything larger
+_SCAN_MAX_BYTES = 2**32 - 2**16
+
+
+def collapse_layout_by_stride(t: torch.Tensor) -> Tuple[List[int], List[int]]:
+    """collapse_layout() for consumers that do not care about element order
+    (a count): dims are sorted by stride before jointly contiguous
+    neighbours merge, so a dense transposed or permuted tensor collapses to
+    one run. Stride-0 (expanded) dims are kept, outermost, so every logical
+    element is still visited once. Returns element-unit (sizes, strides),
+    innermost last; the multiset of addresses they enumerate is the
+    tensor's own."""
+    dims = [(st, s) for s, st in zip(t.shape, t.stride()) if s != 1]
+    if not dims:
+        return [1], [1]
+    expanded = [d for d in dims if d[0] == 0]
+    dense = sorted((d for d in dims if d[0] != 0), reverse=True)
+    merged_sizes: List[int] = []
+    merged_strides: List[int] = []
+    for st, s in expanded + dense:
+        if merged_sizes and merged_strides[-1] == st * s:
+            merged_sizes[-1] *= s
+            merged_strides[-1] = st
+        else:
+            merged_sizes.append(s)
+            merged_strides.append(st)
+    return merged_sizes, merged_strides
+
+
+def scan_class(
+    dtype: torch.dtype, stored_dtype: Optional[torch.dtype] = None
+) -> Optional[int]:
+    """Scan-kernel element class of a real ``dtype`` tensor that will be
+    stored as ``stored_dtype`` (None = as is), or None for a dtype that has
+    no non-finite values to count."""
+    code = cast_code(dtype, stored_dtype) if stored_dtype is not None else CAST_NONE
+    if code != CAST_NONE:
+        return _SCAN_STORED_CLASSES[code]
+    return _SCAN_CLASSES.get(dtype)
+
+
+def _scan_view(t: torch.Tensor) -> Optional[torch.Tensor]:
+    """The real strided view whose elements a scan counts, or None when the
+    tensor is not scanned (non-float dtype, quantized, sparse)."""
+    if t.is_quantized or t.layout != torch.strided:
+        return None
+    if t.dtype.is_complex:
+        if t.is_conj():
+            t = t.conj()  # flips the lazy-conjugate bit: same memory
+        t = torch.view_as_real(t)
+    return t if t.dtype in _SCAN_CLASSES else None
+
+
+def _build_scan_item(t: torch.Tensor) -> Optional[PackItem]:
+    """Descriptor of one real float view of at most _SCAN_MAX_BYTES, or None
+    when the kernel cannot take it."""
+    esz = t.element_size()
+    if t.is_neg():
+        return None
+    sizes, strides = collapse_layout_by_stride(t)
+    if strides[-1] == 1:
+        row_elems = sizes[-1]
+        outer_sizes = sizes[:-1]
+        outer_strides_b = [st * esz for st in strides[:-1]]
+    else:
+        row_elems = 1
+        outer_sizes = sizes
+        outer_strides_b = [st * esz for st in strides]
+    if len(outer_sizes) > 6:
+        return None
+    row_bytes = row_elems * esz
+    vec = math.gcd(16, row_bytes)
+    vec = math.gcd(vec, t.data_ptr())
+    for st in outer_strides_b:
+        vec = math.gcd(vec, st if st else 16)
+    if vec < esz:
+        return None  # storage offset splits an element
+    return PackItem(
+        src_ptr=t.data_ptr(),
+        flat_offset=0,
+        nbytes=t.numel() * esz,
+        row_bytes=row_bytes,
+        outer_sizes=outer_sizes,
+        outer_strides=outer_strides_b,
+        vec=vec,
+    )
+
+
+def build_scan_items(
+    tensors: Sequence[torch.Tensor],
+    stored_dtypes: Optional[Sequence[Optional[torch.dtype]]] = None,
+) -> Tuple[List[Optional[List[PackItem]]], List[Optional[int]]]:
+    """Scan-kernel descriptors for a batch, one entry per tensor.
+
+    ``classes[i]`` is the tensor's element class, or None when it is not
+    scanned at all (non-float dtype, quantized, sparse). ``items[i]`` is the
+    list of descriptors whose counts sum to the tensor's: empty without
+    elements, several when the tensor is over the kernel's size cap and was
+    split along dim 0. It is None when the builder declines the tensor and
+    the caller has to count with torch instead: more than 6 outer dims
+    after collapsing, a storage offset that splits an element, or a tensor
+    that splitting cannot bring under the cap. A complex tensor is
+    described through ``torch.view_as_real``: its counts are of components.
+    """
+    if stored_dtypes is None:
+        stored_dtypes = [None] * len(tensors)
+    if len(stored_dtypes) != len(tensors):
+        raise ValueError("stored_dtypes must have one entry per tensor")
+    items: List[Optional[List[PackItem]]] = []
+    classes: List[Optional[int]] = []
+    for t, stored in zip(tensors, stored_dtypes):
+        view = _scan_view(t)
+        cls = None if view is None else scan_class(view.dtype, stored)
+        classes.append(cls)
+        if cls is None:
+            items.append(None)
+            continue
+        pieces = _split_for_scan(view)
+        built = None if pieces is None else [_build_scan_item(p) for p in pieces]
+        if built is None or any(it is None for it in built):
+            items.append(None)
+        else:
+            items.append(built)
+    return items, classes
+
+
+def _split_for_scan(t: torch.Tensor) -> Optional[List[torch.Tensor]]:
+    """``t`` as views of at most the scan cap each: itself, or dim-0 slices
+    of at most the chunk size as the chunker cuts them. None when one dim-0
+    row alone is over the cap."""
+    if t.numel() == 0:
+        return []
+    nbytes = t.numel() * t.element_size()
+    if nbytes <= _SCAN_MAX_BYTES:
+        return [t]
+    if t.dim() == 0:
+        return None
+    row_bytes = nbytes // t.shape[0]
+    max_bytes = min(knobs.get_max_chunk_size_bytes(), _SCAN_MAX_BYTES)
+    if row_bytes > max_bytes:
+        return None
+    rows = max_bytes // row_bytes
+    return [
+        t.narrow(0, off, min(rows, t.shape[0] - off))
+        for off in range(0, t.shape[0], rows)
+    ]
+
+
+def torch_count_nonfinite(
+    t: torch.Tensor, stored_dtype: Optional[torch.dtype] = None
+) -> Tuple[int, int]:
+    """(NaN, Inf) element counts by the torch expression, on the tensor's
+    own device: what the scan kernel must agree with, and the path for
+    anything it declines. (0, 0) for tensors that are not scanned."""
+    view = _scan_view(t)
+    if view is None or view.numel() == 0:
+        return (0, 0)
+    if scan_class(view.dtype, stored_dtype) in _SCAN_STORED_CLASSES.values():
+        view = view.to(stored_dtype)
+    elif view.element_size() == 1:
+        view = view.to(torch.float32)  # fp8: isnan/isinf want a wider type
+    return int(torch.isnan(view).sum()), int(torch.isinf(view).sum())
+
+
 def _items_to_flat(items: List[PackItem]) -> List[int]:
     """Serialize descriptors for the extension: fixed-width int rows."""
     MAXD = 6
@@ -786,6 +987,63 @@ class StagingEngine:
                 got = sum(int(v) for v in hash_t.cpu().tolist()) % (1 << 64)
                 if got != expected_psum[0]:
                     _raise_psum_mismatch(what, expected_psum[0], got)
+
+    # -- non-finite scan ----------------------------------------------------
+
+    def scan_nonfinite(
+        self,
+        tensors: Sequence[torch.Tensor],
+        stored_dtypes: Optional[Sequence[Optional[torch.dtype]]] = None,
+    ) -> List[Tuple[int, int]]:
+        """(NaN, Inf) element counts of each of this device's ``tensors``,
+        from ONE read-only scan-kernel launch over all of them. Blocking.
+
+        Counts are of logical elements: they equal ``torch.isnan(t).sum()``
+        and ``torch.isinf(t).sum()`` for any layout (an expanded dim counts
+        as often as torch counts it), of components for complex tensors.
+        With ``stored_dtypes[i]`` bfloat16/float16 for a float32 tensor they
+        are the counts of ``t.to(stored)``: what a save_dtype snapshot will
+        hold. Non-float, quantized and sparse tensors report (0, 0).
+
+        Tensors build_scan_items() declines are counted with the torch
+        expression instead; so is everything when the extension is disabled
+        by TSAMD_DISABLE_HIP_STAGING=1."""
+        if stored_dtypes is None:
+            stored_dtypes = [None] * len(tensors)
+        if not self._use_ext:
+            return [
+                torch_count_nonfinite(t, st)
+                for t, st in zip(tensors, stored_dtypes)
+            ]
+        per_tensor, classes = build_scan_items(tensors, stored_dtypes)
+        flat_items: List[PackItem] = []
+        flat_classes: List[int] = []
+        owners: List[int] = []
+        for i, (its, cls) in enumerate(zip(per_tensor, classes)):
+            for it in its or ():
+                flat_items.append(it)
+                flat_classes.append(cls)
+                owners.append(i)
+        out = [[0, 0] for _ in tensors]
+        if flat_items:
+            dev_index = self.device.index or 0
+            with torch.cuda.device(dev_index):
+                counts = _csnap.scan_nonfinite(
+                    _items_to_flat(flat_items),
+                    flat_classes,
+                    len(flat_items),
+                    torch.cuda.current_stream().cuda_stream,
+                    dev_index,
+                )
+            for k, i in enumerate(owners):
+                out[i][0] += int(counts[2 * k])
+                out[i][1] += int(counts[2 * k + 1])
+        for i, (its, cls) in enumerate(zip(per_tensor, classes)):
+            if cls is not None and its is None:
+                out[i] = list(
+                    torch_count_nonfinite(tensors[i], stored_dtypes[i])
+                )
+        return [(a, b) for a, b in out]
 
     # -- debug fallback -----------------------------------------------------
 

@@ -32,7 +32,7 @@ from typing import Any, Dict, List, Optional, Set, Tuple, Union
 import torch
 import torch.distributed as dist
 
-from . import knobs
+from . import knobs, nonfinite as _nonfinite
 from .dist_store import LinearBarrier, get_or_create_store
 from .event import Event, log_event
 from .flatten import Flattened, flatten, inflate
@@ -239,15 +239,25 @@ class Snapshot:
         storage_options: Optional[Dict[str, Any]] = None,
         _custom_tensor_prepare_func: Optional[Any] = None,
         save_dtype: SaveDtype = None,
+        nonfinite: Optional[str] = None,
     ) -> "Snapshot":
         """``save_dtype``: store float32 tensors narrowed to
         ``torch.bfloat16`` / ``torch.float16`` — one dtype for everything,
         or a dict from glob pattern (over logical paths; first match wins)
         to dtype. Device tensors are cast inside the staging gather kernel;
-        leaves that are not strided float32 tensors are stored unchanged."""
+        leaves that are not strided float32 tensors are stored unchanged.
+
+        ``nonfinite``: ``"ignore" | "warn" | "error"``, or None for the
+        ``TSAMD_NONFINITE`` knob (default ignore). Other than ignore, every
+        float tensor leaf is scanned for NaN and Inf, as it will be stored,
+        before anything under ``path`` is touched. ``"error"`` raises
+        :class:`NonFiniteStateError` on every rank and leaves an earlier
+        snapshot at ``path`` intact; ``"warn"`` logs the offending leaves
+        and saves."""
         torch._C._log_api_usage_once("torchsnapshot_amd.Snapshot.take")
         cls._validate_app_state(app_state)
         save_dtype_rules = _normalize_save_dtype(save_dtype)
+        nonfinite_policy = _nonfinite.resolve_policy(nonfinite)
         pg_wrapper = PGWrapper(pg)
         unique_id = uuid.uuid4().hex
         event_meta = {"id": unique_id, "rank": pg_wrapper.get_rank(), "api": "take"}
@@ -267,6 +277,7 @@ class Snapshot:
                     is_async=False,
                     custom_tensor_prepare_func=_custom_tensor_prepare_func,
                     save_dtype_rules=save_dtype_rules,
+                    nonfinite_policy=nonfinite_policy,
                 )
                 pending_io_work.complete()
                 from .integrity import write_checksum_file
@@ -295,11 +306,15 @@ class Snapshot:
         storage_options: Optional[Dict[str, Any]] = None,
         _custom_tensor_prepare_func: Optional[Any] = None,
         save_dtype: SaveDtype = None,
+        nonfinite: Optional[str] = None,
     ) -> "PendingSnapshot":
-        """See :meth:`take` for ``save_dtype``."""
+        """See :meth:`take` for ``save_dtype`` and ``nonfinite``; a
+        :class:`NonFiniteStateError` is raised here, not by the pending
+        snapshot."""
         torch._C._log_api_usage_once("torchsnapshot_amd.Snapshot.async_take")
         cls._validate_app_state(app_state)
         save_dtype_rules = _normalize_save_dtype(save_dtype)
+        nonfinite_policy = _nonfinite.resolve_policy(nonfinite)
         pg_wrapper = PGWrapper(pg)
         unique_id = uuid.uuid4().hex
         event_meta = {
@@ -333,6 +348,7 @@ class Snapshot:
                 is_async=True,
                 custom_tensor_prepare_func=_custom_tensor_prepare_func,
                 save_dtype_rules=save_dtype_rules,
+                nonfinite_policy=nonfinite_policy,
             )
             # once staging is complete, the app may mutate its state
             # freely. With shadow clones (sources_immutable) there is
@@ -372,6 +388,7 @@ class Snapshot:
         is_async: bool,
         custom_tensor_prepare_func: Optional[Any] = None,
         save_dtype_rules: Optional[List[Tuple[str, torch.dtype]]] = None,
+        nonfinite_policy: str = "ignore",
     ) -> Tuple[PendingIOWork, SnapshotMetadata]:
         rank = pg_wrapper.get_rank()
         world_size = pg_wrapper.get_world_size()
@@ -420,6 +437,21 @@ class Snapshot:
         sources_immutable = False
         if is_async:
             sources_immutable = cls._shadow_for_async(flattened)
+
+        # non-finite policy: scan what will be staged (the hook's output,
+        # the async shadow) while refusing is still free. Nothing under the
+        # path has been touched yet: prepare_write and _uncommit come later,
+        # so an earlier commit survives a refusal. Every rank learns every
+        # rank's findings and takes the same decision.
+        if nonfinite_policy != "ignore":
+            _nonfinite.enforce(
+                nonfinite_policy,
+                _nonfinite.scan_leaves(
+                    flattened,
+                    lambda p, obj: _resolve_save_dtype(save_dtype_rules, p, obj),
+                ),
+                pg_wrapper,
+            )
 
         write_reqs: List[WriteReq] = []
         req_to_logical: Dict[str, str] = {}
