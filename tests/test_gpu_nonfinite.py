@@ -259,7 +259,7 @@ def test_declined_layout_takes_torch_path(monkeypatch):
 
 
 def test_split_under_small_cap(monkeypatch):
-    monkeypatch.setattr(staging, "_SCAN_MAX_BYTES", 4096)
+    monkeypatch.setattr(staging, "_KERNEL_MAX_BYTES", 4096)
     t = _planted(1000, 10)
     its, _ = _items(t)
     assert len(its) == 10 and all(it.nbytes <= 4096 for it in its)

@@ -127,6 +127,82 @@ def test_scatter_h2d_round_trip():
         assert torch.equal(s, d)
 
 
+def _gather_edge_layouts():
+    """The scan suite's work-unit-edge layouts (test_gpu_nonfinite.py's
+    _edge_layouts), every element distinct: just over three 64 KiB work
+    units each, so units start and end inside rows and inside vectors'
+    strides."""
+
+    def distinct(*shape, start):
+        n = 1
+        for s in shape:
+            n *= s
+        return torch.arange(
+            start, start + n, dtype=torch.int32, device="cuda"
+        ).reshape(shape)
+
+    contig = distinct(3 * 16384 + 1, start=1)  # 3 * 64 KiB + 4 bytes
+    # 2064 B rows: wide, and no work-unit boundary falls on a row start
+    wide = distinct(97, 524, start=1 << 20)[:, 4:520]
+    narrow = distinct(16385, 8, start=1 << 24)[:, 1:4]  # 12 B rows
+    return {"contig": contig, "wide": wide, "narrow": narrow}
+
+
+@pytest.mark.parametrize("hashed", [False, True], ids=["plain", "hash"])
+@pytest.mark.parametrize("mode", ["direct", "slab"])
+@pytest.mark.parametrize("which", ["contig", "wide", "narrow", "batch"])
+def test_gather_work_unit_edges(which, mode, hashed):
+    """Plain gather across work-unit boundaries, for each traversal and
+    with all three layouts in one launch (the owner search then crosses
+    descriptors mid-grid): bytes equal t.contiguous()'s, and the fused
+    psum64 equals the CPU verifier's over those bytes at slab offsets."""
+    from torchsnapshot_amd import _csnap, integrity
+    from torchsnapshot_amd.ops.staging import _items_to_flat, build_pack_items
+
+    layouts = _gather_edge_layouts()
+    tensors = list(layouts.values()) if which == "batch" else [layouts[which]]
+    items, offsets, total = build_pack_items(tensors)
+    for it, t in zip(items, tensors):
+        assert it.nbytes > 3 * 65536 and it.cast == 0
+        if t is layouts["contig"]:
+            assert it.nbytes == 3 * 65536 + 4 and not it.outer_sizes
+        elif t is layouts["wide"]:
+            assert it.row_bytes == 2064 and it.outer_sizes == [97]
+            assert it.vec == 16
+        else:
+            assert it.row_bytes == 12 and it.vec == 4
+    pinned = torch.full((total,), 0xA5, dtype=torch.uint8).pin_memory()
+    slab = None
+    if mode == "slab":
+        slab = torch.full((total,), 0xA5, dtype=torch.uint8, device="cuda")
+    hash_t = None
+    if hashed:
+        hash_t = torch.zeros(len(items), dtype=torch.uint64, device="cuda")
+    torch.cuda.synchronize()
+    h = _csnap.pack_d2h(
+        _items_to_flat(items), len(items),
+        slab.data_ptr() if slab is not None else 0,
+        pinned.data_ptr(), total, torch.cuda.current_stream().cuda_stream, 0,
+        hash_t.data_ptr() if hash_t is not None else 0,
+    )
+    _csnap.wait(h)
+    got = bytes(pinned.numpy())
+    hashes = hash_t.cpu().tolist() if hashed else None
+    end = 0
+    for i, (t, it, off) in enumerate(zip(tensors, items, offsets)):
+        want = _ref_bytes(t)
+        assert len(want) == it.nbytes
+        assert got[off : off + it.nbytes] == want, f"member {i}"
+        # the alignment gap before this member is untouched
+        assert got[end:off] == b"\xa5" * (off - end), f"gap before {i}"
+        end = off + it.nbytes
+        if hashed:
+            value = int(hashes[i]) % (1 << 64)
+            digest = integrity.psum64_hexdigest(want, word_base=off // 8)
+            assert "psum64:" + format(value, "016x") == digest, f"member {i}"
+    assert got[end:] == b"\xa5" * (total - end)
+
+
 def test_snapshot_gpu_round_trip():
     sd = StateDict(
         fp8=torch.randn(512, 256).to(torch.float8_e4m3fn).cuda(),

@@ -217,7 +217,7 @@ def test_not_scanned():
 
 
 def test_split_at_small_cap(monkeypatch):
-    monkeypatch.setattr(staging, "_SCAN_MAX_BYTES", 1024)
+    monkeypatch.setattr(staging, "_KERNEL_MAX_BYTES", 1024)
     t = _planted(100, 10)  # 4000 bytes: rows of 40, 25 rows per piece
     (its,), (cls,) = staging.build_scan_items([t])
     assert [it.nbytes for it in its] == [1000] * 4
@@ -241,10 +241,10 @@ def test_split_at_small_cap(monkeypatch):
 
 def test_real_size_cap():
     """The builder's cap is the extension's: 2^32 - 64 KiB bytes is the
-    largest single descriptor (check_scan_descs refuses only nbytes above
+    largest single descriptor (check_descs refuses only nbytes above
     it), and anything larger is split into pieces under it."""
     cap = 2**32 - 2**16
-    assert staging._SCAN_MAX_BYTES == cap
+    assert staging._KERNEL_MAX_BYTES == cap
     row = torch.zeros(1, 16384)  # expanded: no 4 GiB allocation
     (its,), _ = staging.build_scan_items([row.expand(65535, 16384)])
     assert [it.nbytes for it in its] == [cap]

@@ -19,7 +19,11 @@ PKG_ROOT = Path(__file__).resolve().parent.parent
 SRC = PKG_ROOT / "ops" / "hip" / "staging.hip"
 # everything the translation unit reads: the extension is rebuilt when any
 # of these is newer than it
-DEPS = (SRC, PKG_ROOT / "ops" / "hip" / "file_sink.h")
+DEPS = (
+    SRC,
+    PKG_ROOT / "ops" / "hip" / "desc_check.h",
+    PKG_ROOT / "ops" / "hip" / "file_sink.h",
+)
 OUT = PKG_ROOT / f"_csnap{sysconfig.get_config_var('EXT_SUFFIX') or '.so'}"
 
 GFX_ARCH = os.environ.get("TSAMD_GFX_ARCH", "gfx950")

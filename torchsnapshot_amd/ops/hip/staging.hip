@@ -9,13 +9,29 @@
 //     :104-162, and its tensor.cpu() staging, io_preparers/tensor.py:353)
 //   - gather-and-cast: per-descriptor f32 -> bf16/f16 narrowing fused into
 //     the same launch (save_dtype), so only stored-size bytes leave the GPU
-//   - scatter kernel (same code path, direction-reversed) for restore, with
-//     bf16/f16 -> f32 widening and the psum64 check fused into the launch
+//   - scatter kernel for restore (and for scatter_h2d), with bf16/f16 ->
+//     f32 widening and the psum64 check fused into the launch
 //   - scan kernel: NaN / Inf counts per tensor over the same descriptors,
 //     read-only, one launch for the whole state (the nonfinite= policy)
 //   - SDMA copies (hipMemcpyAsync) slab <-> pinned host memory; the slab
 //     can also be skipped entirely ("direct" mode): the kernel writes
 //     gathered bytes straight into pinned host memory over PCIe
+//
+// How the kernels are put together. There is one of each of these, and
+// every kernel is a composition of them:
+//   - for_each_work_unit: grid-stride loop over 64 KiB work units, the
+//     owner search over the prefix sums, the unit's byte range [s, e)
+//   - for_each_vec<VEC, TS>: the three-way traversal of that range
+//     (contiguous / wide rows / narrow rows), calling a lane operation
+//     with (flat index, tensor address). TS = tensor bytes per flat byte:
+//     1 for copy, scatter and scan, 2 for cast and widen
+//   - lane operations: copy_vec (+ psum_contrib), cast_vec, scatter_vec,
+//     widen_vec, scan_vec. Each kernel family differs only in this
+//   - add_per_wave: wave64 reduction and one atomic per wave, for the u64
+//     hashes and the u32 counters alike
+//   - on the host (desc_check.h): parse_descs + check_descs validate every
+//     descriptor before the GPU is touched; wu_prefix_of, grid_for and
+//     LaunchTables are the launch prologue of both launchers
 //
 // Design notes (CDNA4):
 //   - wave64; block = 256 threads; work units of 64 KiB of slab bytes,
@@ -24,8 +40,10 @@
 //     widest vector the layout allows (16 B/lane -> 1 KiB per wave per
 //     instruction); narrow rows copy lane-per-row so writes to the slab
 //     stay coalesced across lanes even when reads are scattered
-//   - all within-tensor indices fit u32 (tensors are chunked to <= 512 MB
-//     upstream); row->coordinate decomposition uses u32 div/mod
+//   - all within-tensor indices fit u32 (check_descs caps a descriptor at
+//     4 GiB - 64 KiB; tensors are chunked to <= 512 MB upstream);
+//     row->coordinate decomposition uses u32 div/mod. Tensor-side offsets
+//     are 64-bit: under a cast they are twice the flat index
 //
 // Deliberately torch-free: tensors enter as raw pointers; stream ordering
 // against the producer is a caller-provided stream handle we event-chain.
@@ -44,6 +62,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "desc_check.h"
 #include "file_sink.h"
 
 namespace py = pybind11;
@@ -59,35 +78,11 @@ namespace py = pybind11;
 
 namespace {
 
-constexpr int kMaxDims = 6;
-constexpr uint32_t kWorkUnitBytes = 64 * 1024;
+// Desc, the cast and scan codes, kWorkUnitBytes and the host-side checks
+using namespace tsamd;
+
 constexpr int kBlockThreads = 256;
 constexpr uint32_t kWideRowBytes = 2048;
-
-struct Desc {
-  const char* tensor_base;
-  unsigned long long flat_off;   // byte offset of this tensor in the slab
-  uint32_t nbytes;               // payload bytes (< 2^32 by construction)
-  uint32_t row_bytes;            // innermost contiguous run
-  uint32_t vec;                  // safe vector width (16/8/4/2/1)
-  uint32_t ndim;                 // number of outer (strided) dims
-  uint32_t sizes[kMaxDims];
-  long long strides[kMaxDims];   // byte strides of outer dims
-  // narrowing cast fused into the gather: 0 none, 1 f32->bf16, 2 f32->f16.
-  // With a cast, every flat-side quantity above (nbytes, row_bytes,
-  // flat_off, vec) is in DESTINATION bytes; tensor_base and strides stay
-  // in source bytes. A lane writes `vec` bytes and reads 2*vec.
-  // Scatter only: 3 bf16->f32, 4 f16->f32 widening, same convention (flat
-  // side in stored 2-byte units, tensor side in f32 bytes): a lane reads
-  // `vec` stored bytes and writes 2*vec.
-  uint32_t cast;
-};
-
-constexpr uint32_t kCastNone = 0;
-constexpr uint32_t kCastBF16 = 1;
-constexpr uint32_t kCastF16 = 2;
-constexpr uint32_t kCastBF16toF32 = 3;
-constexpr uint32_t kCastF16toF32 = 4;
 
 // ---------------------------------------------------------------------------
 // psum64 checksum: an order-independent weighted word sum over the flat
@@ -146,31 +141,123 @@ __device__ inline unsigned long long row_offset(const Desc& d, uint32_t row) {
   return off;
 }
 
-template <int VEC, bool GATHER>
-__device__ inline void copy_vec(char* flat, const char* strided) {
-  if (GATHER) {
-    if (VEC == 16)
-      *reinterpret_cast<uint4*>(flat) = *reinterpret_cast<const uint4*>(strided);
-    else if (VEC == 8)
-      *reinterpret_cast<uint64_t*>(flat) = *reinterpret_cast<const uint64_t*>(strided);
-    else if (VEC == 4)
-      *reinterpret_cast<uint32_t*>(flat) = *reinterpret_cast<const uint32_t*>(strided);
-    else if (VEC == 2)
-      *reinterpret_cast<uint16_t*>(flat) = *reinterpret_cast<const uint16_t*>(strided);
-    else
-      *flat = *strided;
-  } else {
-    if (VEC == 16)
-      *reinterpret_cast<uint4*>(const_cast<char*>(strided)) = *reinterpret_cast<const uint4*>(flat);
-    else if (VEC == 8)
-      *reinterpret_cast<uint64_t*>(const_cast<char*>(strided)) = *reinterpret_cast<const uint64_t*>(flat);
-    else if (VEC == 4)
-      *reinterpret_cast<uint32_t*>(const_cast<char*>(strided)) = *reinterpret_cast<const uint32_t*>(flat);
-    else if (VEC == 2)
-      *reinterpret_cast<uint16_t*>(const_cast<char*>(strided)) = *reinterpret_cast<const uint16_t*>(flat);
-    else
-      *const_cast<char*>(strided) = *flat;
+// ---------------------------------------------------------------------------
+// The traversal: visit [s, e) of one descriptor's flat byte range, VEC
+// flat bytes per call, as op(flat_index, tensor_address). TS is the number
+// of tensor bytes per flat byte (2 under a cast: the tensor side is f32,
+// the flat side 16-bit), applied in 64 bits: a contiguous tensor just
+// under 4 GiB stored has just under 8 GiB of f32. The flat index is handed
+// over widened to 64 bits as row start + lane offset, so that `flat + index`
+// in a lane operation splits into a per-row base and a small offset; as a
+// u32 sum it cost the cast and widen kernels 6-8 VGPRs and one wave of
+// occupancy (profiles/traversal_refactor_measurements.md). UNROLL > 1 asks
+// for that unroll of the contiguous loop (the scan's loads are independent
+// and its body is small; the copies are left to the compiler).
+// ---------------------------------------------------------------------------
+
+template <int VEC, int TS, int UNROLL = 1, typename Op>
+__device__ __forceinline__ void for_each_vec(const Desc& d, uint32_t s,
+                                             uint32_t e, Op op) {
+  const uint32_t tid = threadIdx.x;
+  const uint32_t rb = d.row_bytes;
+  const char* base = d.tensor_base;
+  if (d.ndim == 0 || rb == d.nbytes) {
+    // fully contiguous: lanes across [s, e)
+    if constexpr (UNROLL > 1) {
+#pragma unroll UNROLL
+      for (uint32_t i = s + tid * VEC; i < e; i += kBlockThreads * VEC) {
+        op(i, base + (unsigned long long)TS * i);
+      }
+    } else {
+      for (uint32_t i = s + tid * VEC; i < e; i += kBlockThreads * VEC) {
+        op(i, base + (unsigned long long)TS * i);
+      }
+    }
+    return;
   }
+  if (rb >= kWideRowBytes) {
+    // wide rows: rows sequential, lanes across columns
+    uint32_t row = s / rb;
+    uint32_t col = s - row * rb;
+    uint32_t off = s;
+    while (off < e) {
+      const char* p = base + row_offset(d, row) + (unsigned long long)TS * col;
+      uint32_t n = min(rb - col, e - off);
+      for (uint32_t i = tid * VEC; i < n; i += kBlockThreads * VEC) {
+        op((unsigned long long)off + i, p + (unsigned long long)TS * i);
+      }
+      off += n;
+      ++row;
+      col = 0;
+    }
+  } else {
+    // narrow rows: one lane per row; flat-side access stays coalesced
+    uint32_t first_row = s / rb;
+    uint32_t last_row = (e - 1) / rb;
+    for (uint32_t r = first_row + tid; r <= last_row; r += kBlockThreads) {
+      const char* p = base + row_offset(d, r);
+      uint32_t flat_pos = r * rb;
+      uint32_t lo = flat_pos < s ? (s - flat_pos) : 0;
+      uint32_t hi = (flat_pos + rb > e) ? (e - flat_pos) : rb;
+      for (uint32_t i = lo; i < hi; i += VEC) {
+        op((unsigned long long)flat_pos + i, p + (unsigned long long)TS * i);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The work-unit driver: grid-stride over all work units of the batch,
+// find the descriptor that owns each, and hand body(owner, desc, s, e)
+// the unit's flat byte range. check_descs caps nbytes at 2^32 - 64 KiB,
+// and `e` is formed without adding to `s` first, so nothing here or in
+// the traversal wraps a u32.
+// ---------------------------------------------------------------------------
+
+template <typename Body>
+__device__ __forceinline__ void for_each_work_unit(
+    const Desc* __restrict__ descs, int n,
+    const unsigned long long* __restrict__ wu_prefix,
+    unsigned long long total_wus, Body body) {
+  for (unsigned long long wu = blockIdx.x; wu < total_wus; wu += gridDim.x) {
+    // binary search: which tensor owns this work unit
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+      int mid = (lo + hi + 1) >> 1;
+      if (wu_prefix[mid] <= wu) lo = mid;
+      else hi = mid - 1;
+    }
+    const Desc d = descs[lo];
+    unsigned long long local_wu = wu - wu_prefix[lo];
+    uint32_t s = (uint32_t)(local_wu * kWorkUnitBytes);
+    uint32_t e = d.nbytes - s > kWorkUnitBytes ? s + kWorkUnitBytes : d.nbytes;
+    body(lo, d, s, e);
+  }
+}
+
+// wave64 reduction, then one atomic per wave per work unit (none for zero)
+template <typename T>
+__device__ __forceinline__ void add_per_wave(unsigned long long* dst, T v) {
+  for (int delta = 32; delta > 0; delta >>= 1) {
+    v += __shfl_down(v, delta, 64);
+  }
+  if ((threadIdx.x & 63) == 0 && v != 0) {
+    atomicAdd(dst, (unsigned long long)v);
+  }
+}
+
+template <int VEC>
+__device__ inline void copy_vec(char* flat, const char* strided) {
+  if (VEC == 16)
+    *reinterpret_cast<uint4*>(flat) = *reinterpret_cast<const uint4*>(strided);
+  else if (VEC == 8)
+    *reinterpret_cast<uint64_t*>(flat) = *reinterpret_cast<const uint64_t*>(strided);
+  else if (VEC == 4)
+    *reinterpret_cast<uint32_t*>(flat) = *reinterpret_cast<const uint32_t*>(strided);
+  else if (VEC == 2)
+    *reinterpret_cast<uint16_t*>(flat) = *reinterpret_cast<const uint16_t*>(strided);
+  else
+    *flat = *strided;
 }
 
 // Scatter VEC flat bytes into the strided tensor. When HASH, returns the
@@ -214,74 +301,33 @@ __device__ inline unsigned long long scatter_vec(
   return h;
 }
 
-// Copy [s, e) of the tensor's flat byte range for one work unit. When
-// HASH, returns this thread's psum64 contribution. Gather hashes at slab
-// offsets (d.flat_off); scatter hashes at `hash_off`, the file offset of
-// the descriptor's first flat byte.
-template <int VEC, bool GATHER, bool HASH>
-__device__ unsigned long long process_range(const Desc& d, char* flat_base,
-                                            uint32_t s, uint32_t e,
-                                            unsigned long long hash_off = 0) {
+// Gather [s, e) of the tensor's flat byte range for one work unit. When
+// HASH, returns this thread's psum64 contribution at slab offsets.
+template <int VEC, bool HASH>
+__device__ unsigned long long gather_range(const Desc& d, char* flat_base,
+                                           uint32_t s, uint32_t e) {
   char* flat = flat_base + d.flat_off;
-  const uint32_t tid = threadIdx.x;
-  const uint32_t rb = d.row_bytes;
   unsigned long long h = 0;
-  if (d.ndim == 0 || rb == d.nbytes) {
-    // fully contiguous: plain vectorized copy of [s, e)
-    const char* src = d.tensor_base;
-    for (uint32_t i = s + tid * VEC; i < e; i += kBlockThreads * VEC) {
-      if (GATHER) {
-        copy_vec<VEC, GATHER>(flat + i, src + i);
-        if (HASH) h += psum_contrib<VEC>(src + i, d.flat_off + i);
-      } else {
-        h += scatter_vec<VEC, HASH>(const_cast<char*>(src) + i, flat + i,
-                                    hash_off + i);
-      }
-    }
-    return h;
-  }
-  if (rb >= kWideRowBytes) {
-    // wide rows: rows sequential, lanes across columns
-    uint32_t row = s / rb;
-    uint32_t col = s - row * rb;
-    uint32_t off = s;
-    while (off < e) {
-      const char* src = d.tensor_base + row_offset(d, row);
-      uint32_t n = min(rb - col, e - off);
-      for (uint32_t i = tid * VEC; i < n; i += kBlockThreads * VEC) {
-        if (GATHER) {
-          copy_vec<VEC, GATHER>(flat + off + i, src + col + i);
-          if (HASH) h += psum_contrib<VEC>(src + col + i, d.flat_off + off + i);
-        } else {
-          h += scatter_vec<VEC, HASH>(const_cast<char*>(src) + col + i,
-                                      flat + off + i, hash_off + off + i);
-        }
-      }
-      off += n;
-      ++row;
-      col = 0;
-    }
-  } else {
-    // narrow rows: one lane per row; slab-side access stays coalesced
-    uint32_t first_row = s / rb;
-    uint32_t last_row = (e - 1) / rb;
-    for (uint32_t r = first_row + tid; r <= last_row; r += kBlockThreads) {
-      const char* src = d.tensor_base + row_offset(d, r);
-      uint32_t flat_pos = r * rb;
-      uint32_t lo = flat_pos < s ? (s - flat_pos) : 0;
-      uint32_t hi = (flat_pos + rb > e) ? (e - flat_pos) : rb;
-      for (uint32_t i = lo; i < hi; i += VEC) {
-        if (GATHER) {
-          copy_vec<VEC, GATHER>(flat + flat_pos + i, src + i);
-          if (HASH) h += psum_contrib<VEC>(src + i, d.flat_off + flat_pos + i);
-        } else {
-          h += scatter_vec<VEC, HASH>(const_cast<char*>(src) + i,
-                                      flat + flat_pos + i,
-                                      hash_off + flat_pos + i);
-        }
-      }
-    }
-  }
+  for_each_vec<VEC, 1>(d, s, e, [&](unsigned long long i, const char* src) {
+    copy_vec<VEC>(flat + i, src);
+    if (HASH) h += psum_contrib<VEC>(src, d.flat_off + i);
+  });
+  return h;
+}
+
+// Scatter counterpart: hashes at `hash_off`, the file offset of the
+// descriptor's first flat byte.
+template <int VEC, bool HASH>
+__device__ unsigned long long scatter_range(const Desc& d,
+                                            const char* flat_base, uint32_t s,
+                                            uint32_t e,
+                                            unsigned long long hash_off) {
+  const char* flat = flat_base + d.flat_off;
+  unsigned long long h = 0;
+  for_each_vec<VEC, 1>(d, s, e, [&](unsigned long long i, const char* dst) {
+    h += scatter_vec<VEC, HASH>(const_cast<char*>(dst), flat + i,
+                                hash_off + i);
+  });
   return h;
 }
 
@@ -383,109 +429,52 @@ __device__ inline unsigned long long cast_vec(char* flat, const char* src,
   return h;
 }
 
-// Cast counterpart of process_range: [s, e) and every index below are in
-// destination (flat-side) bytes; the source sits at twice the offset,
-// computed in 64 bits (a contiguous tensor just under 4 GiB stored has
-// just under 8 GiB of source).
+// Cast counterpart of gather_range: [s, e) is in destination (flat-side)
+// bytes, the f32 source sits at twice the offset.
 template <int VEC, bool HASH>
-__device__ unsigned long long process_range_cast(const Desc& d,
-                                                 char* flat_base, uint32_t s,
-                                                 uint32_t e) {
+__device__ unsigned long long cast_range(const Desc& d, char* flat_base,
+                                         uint32_t s, uint32_t e) {
   char* flat = flat_base + d.flat_off;
-  const uint32_t tid = threadIdx.x;
-  const uint32_t rb = d.row_bytes;
   const uint32_t code = d.cast;
   unsigned long long h = 0;
-  if (d.ndim == 0 || rb == d.nbytes) {
-    const char* src = d.tensor_base;
-    for (uint32_t i = s + tid * VEC; i < e; i += kBlockThreads * VEC) {
-      h += cast_vec<VEC, HASH>(flat + i, src + 2ull * i, code, d.flat_off + i);
-    }
-    return h;
-  }
-  if (rb >= kWideRowBytes) {
-    // wide rows: rows sequential, lanes across columns
-    uint32_t row = s / rb;
-    uint32_t col = s - row * rb;
-    uint32_t off = s;
-    while (off < e) {
-      const char* src = d.tensor_base + row_offset(d, row) + 2ull * col;
-      uint32_t n = min(rb - col, e - off);
-      for (uint32_t i = tid * VEC; i < n; i += kBlockThreads * VEC) {
-        h += cast_vec<VEC, HASH>(flat + off + i, src + 2ull * i, code,
-                                 d.flat_off + off + i);
-      }
-      off += n;
-      ++row;
-      col = 0;
-    }
-  } else {
-    // narrow rows: one lane per row; flat-side writes stay coalesced
-    uint32_t first_row = s / rb;
-    uint32_t last_row = (e - 1) / rb;
-    for (uint32_t r = first_row + tid; r <= last_row; r += kBlockThreads) {
-      const char* src = d.tensor_base + row_offset(d, r);
-      uint32_t flat_pos = r * rb;
-      uint32_t lo = flat_pos < s ? (s - flat_pos) : 0;
-      uint32_t hi = (flat_pos + rb > e) ? (e - flat_pos) : rb;
-      for (uint32_t i = lo; i < hi; i += VEC) {
-        h += cast_vec<VEC, HASH>(flat + flat_pos + i, src + 2ull * i, code,
-                                 d.flat_off + flat_pos + i);
-      }
-    }
-  }
+  for_each_vec<VEC, 2>(d, s, e, [&](unsigned long long i, const char* src) {
+    h += cast_vec<VEC, HASH>(flat + i, src, code, d.flat_off + i);
+  });
   return h;
 }
 
-// CAST instantiations additionally route descriptors with a cast code to
-// process_range_cast; they are launched only for batches that contain one,
-// so uncast batches run exactly the kernels they always did.
-template <bool GATHER, bool HASH, bool CAST = false>
+// Gather kernel; when HASH, hash_out[i] accumulates the psum64 of
+// descriptor i's bytes at slab offsets. CAST instantiations additionally
+// route descriptors with a cast code to cast_range; they are launched only
+// for batches that contain one.
+template <bool HASH, bool CAST>
 __global__ __launch_bounds__(kBlockThreads) void pack_kernel(
     const Desc* __restrict__ descs, int n,
     const unsigned long long* __restrict__ wu_prefix,
     unsigned long long total_wus, char* __restrict__ flat_base,
     unsigned long long* __restrict__ hash_out) {
-  for (unsigned long long wu = blockIdx.x; wu < total_wus; wu += gridDim.x) {
-    // binary search: which tensor owns this work unit
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-      int mid = (lo + hi + 1) >> 1;
-      if (wu_prefix[mid] <= wu) lo = mid;
-      else hi = mid - 1;
-    }
-    const Desc d = descs[lo];
-    unsigned long long local_wu = wu - wu_prefix[lo];
-    uint32_t s = (uint32_t)(local_wu * kWorkUnitBytes);
-    uint32_t e = s + kWorkUnitBytes > d.nbytes ? d.nbytes
-                                               : s + kWorkUnitBytes;
-    unsigned long long h = 0;
-    if (CAST && d.cast != kCastNone) {
-      switch (d.vec) {
-        case 16: h = process_range_cast<16, HASH>(d, flat_base, s, e); break;
-        case 8: h = process_range_cast<8, HASH>(d, flat_base, s, e); break;
-        case 4: h = process_range_cast<4, HASH>(d, flat_base, s, e); break;
-        default: h = process_range_cast<2, HASH>(d, flat_base, s, e); break;
-      }
-    } else {
-      switch (d.vec) {
-        case 16: h = process_range<16, GATHER, HASH>(d, flat_base, s, e); break;
-        case 8: h = process_range<8, GATHER, HASH>(d, flat_base, s, e); break;
-        case 4: h = process_range<4, GATHER, HASH>(d, flat_base, s, e); break;
-        case 2: h = process_range<2, GATHER, HASH>(d, flat_base, s, e); break;
-        default: h = process_range<1, GATHER, HASH>(d, flat_base, s, e); break;
-      }
-    }
-    if (HASH) {
-      // wave64 reduction, then one atomic per wave per work unit
-      for (int delta = 32; delta > 0; delta >>= 1) {
-        h += __shfl_down(h, delta, 64);
-      }
-      if ((threadIdx.x & 63) == 0 && h != 0) {
-        atomicAdd(&hash_out[lo], h);
-      }
-    }
-  }
+  for_each_work_unit(
+      descs, n, wu_prefix, total_wus,
+      [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
+        unsigned long long h = 0;
+        if (CAST && d.cast != kCastNone) {
+          switch (d.vec) {
+            case 16: h = cast_range<16, HASH>(d, flat_base, s, e); break;
+            case 8: h = cast_range<8, HASH>(d, flat_base, s, e); break;
+            case 4: h = cast_range<4, HASH>(d, flat_base, s, e); break;
+            default: h = cast_range<2, HASH>(d, flat_base, s, e); break;
+          }
+        } else {
+          switch (d.vec) {
+            case 16: h = gather_range<16, HASH>(d, flat_base, s, e); break;
+            case 8: h = gather_range<8, HASH>(d, flat_base, s, e); break;
+            case 4: h = gather_range<4, HASH>(d, flat_base, s, e); break;
+            case 2: h = gather_range<2, HASH>(d, flat_base, s, e); break;
+            default: h = gather_range<1, HASH>(d, flat_base, s, e); break;
+          }
+        }
+        if (HASH) add_per_wave(&hash_out[owner], h);
+      });
 }
 
 // ---------------------------------------------------------------------------
@@ -573,66 +562,30 @@ __device__ inline unsigned long long widen_vec(char* dst, const char* flat,
   return h;
 }
 
-// Widen counterpart of process_range_cast, direction reversed: [s, e) and
-// every index below are in stored (flat-side) bytes; the f32 target sits
-// at twice the offset, computed in 64 bits.
+// Widen counterpart of scatter_range: [s, e) is in stored (flat-side)
+// bytes, the f32 target sits at twice the offset.
 template <int VEC, bool HASH>
-__device__ unsigned long long process_range_widen(const Desc& d,
-                                                  const char* flat_base,
-                                                  uint32_t s, uint32_t e,
-                                                  unsigned long long hash_off) {
+__device__ unsigned long long widen_range(const Desc& d,
+                                          const char* flat_base, uint32_t s,
+                                          uint32_t e,
+                                          unsigned long long hash_off) {
   const char* flat = flat_base + d.flat_off;
-  char* base = const_cast<char*>(d.tensor_base);
-  const uint32_t tid = threadIdx.x;
-  const uint32_t rb = d.row_bytes;
   const uint32_t code = d.cast;
   unsigned long long h = 0;
-  if (d.ndim == 0 || rb == d.nbytes) {
-    for (uint32_t i = s + tid * VEC; i < e; i += kBlockThreads * VEC) {
-      h += widen_vec<VEC, HASH>(base + 2ull * i, flat + i, code, hash_off + i);
-    }
-    return h;
-  }
-  if (rb >= kWideRowBytes) {
-    // wide rows: rows sequential, lanes across columns
-    uint32_t row = s / rb;
-    uint32_t col = s - row * rb;
-    uint32_t off = s;
-    while (off < e) {
-      char* dst = base + row_offset(d, row) + 2ull * col;
-      uint32_t n = min(rb - col, e - off);
-      for (uint32_t i = tid * VEC; i < n; i += kBlockThreads * VEC) {
-        h += widen_vec<VEC, HASH>(dst + 2ull * i, flat + off + i, code,
-                                  hash_off + off + i);
-      }
-      off += n;
-      ++row;
-      col = 0;
-    }
-  } else {
-    // narrow rows: one lane per row; flat-side reads stay coalesced
-    uint32_t first_row = s / rb;
-    uint32_t last_row = (e - 1) / rb;
-    for (uint32_t r = first_row + tid; r <= last_row; r += kBlockThreads) {
-      char* dst = base + row_offset(d, r);
-      uint32_t flat_pos = r * rb;
-      uint32_t lo = flat_pos < s ? (s - flat_pos) : 0;
-      uint32_t hi = (flat_pos + rb > e) ? (e - flat_pos) : rb;
-      for (uint32_t i = lo; i < hi; i += VEC) {
-        h += widen_vec<VEC, HASH>(dst + 2ull * i, flat + flat_pos + i, code,
-                                  hash_off + flat_pos + i);
-      }
-    }
-  }
+  for_each_vec<VEC, 2>(d, s, e, [&](unsigned long long i, const char* dst) {
+    h += widen_vec<VEC, HASH>(const_cast<char*>(dst), flat + i, code,
+                              hash_off + i);
+  });
   return h;
 }
 
-// Restore kernel: scatter (and, when WIDEN, widen) flat bytes into strided
-// device tensors; when HASH, hash_out[i] accumulates the psum64 of
-// descriptor i's flat bytes at file offset hash_byte0 + flat_off. A kernel
-// of its own rather than more pack_kernel instantiations: the extra
-// argument would otherwise change every gather kernel's signature. The
-// host caps nbytes at 2^32 - 64 KiB so no u32 index below can wrap.
+// Scatter kernel (restore, and scatter_h2d): flat bytes into strided
+// device tensors, widening when WIDEN; when HASH, hash_out[i] accumulates
+// the psum64 of descriptor i's flat bytes at file offset hash_byte0 +
+// flat_off. It is the gather with the lane operation reversed: same
+// driver, same traversal. It stays a kernel of its own because its flat
+// side is read-only and its hash offsets are file offsets, which takes
+// one more argument than the gather has.
 template <bool HASH, bool WIDEN>
 __global__ __launch_bounds__(kBlockThreads) void unpack_kernel(
     const Desc* __restrict__ descs, int n,
@@ -640,79 +593,44 @@ __global__ __launch_bounds__(kBlockThreads) void unpack_kernel(
     unsigned long long total_wus, const char* __restrict__ flat_base,
     unsigned long long* __restrict__ hash_out,
     unsigned long long hash_byte0) {
-  for (unsigned long long wu = blockIdx.x; wu < total_wus; wu += gridDim.x) {
-    // binary search: which tensor owns this work unit
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-      int mid = (lo + hi + 1) >> 1;
-      if (wu_prefix[mid] <= wu) lo = mid;
-      else hi = mid - 1;
-    }
-    const Desc d = descs[lo];
-    unsigned long long local_wu = wu - wu_prefix[lo];
-    uint32_t s = (uint32_t)(local_wu * kWorkUnitBytes);
-    uint32_t e = d.nbytes - s > kWorkUnitBytes ? s + kWorkUnitBytes : d.nbytes;
-    const unsigned long long ho = hash_byte0 + d.flat_off;
-    char* fb = const_cast<char*>(flat_base);
-    unsigned long long h = 0;
-    if (WIDEN && d.cast != kCastNone) {
-      switch (d.vec) {
-        case 16: h = process_range_widen<16, HASH>(d, fb, s, e, ho); break;
-        case 8: h = process_range_widen<8, HASH>(d, fb, s, e, ho); break;
-        case 4: h = process_range_widen<4, HASH>(d, fb, s, e, ho); break;
-        default: h = process_range_widen<2, HASH>(d, fb, s, e, ho); break;
-      }
-    } else {
-      switch (d.vec) {
-        case 16: h = process_range<16, false, HASH>(d, fb, s, e, ho); break;
-        case 8: h = process_range<8, false, HASH>(d, fb, s, e, ho); break;
-        case 4: h = process_range<4, false, HASH>(d, fb, s, e, ho); break;
-        case 2: h = process_range<2, false, HASH>(d, fb, s, e, ho); break;
-        default: h = process_range<1, false, HASH>(d, fb, s, e, ho); break;
-      }
-    }
-    if (HASH) {
-      // wave64 reduction, then one atomic per wave per work unit
-      for (int delta = 32; delta > 0; delta >>= 1) {
-        h += __shfl_down(h, delta, 64);
-      }
-      if ((threadIdx.x & 63) == 0 && h != 0) {
-        atomicAdd(&hash_out[lo], h);
-      }
-    }
-  }
+  for_each_work_unit(
+      descs, n, wu_prefix, total_wus,
+      [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
+        const unsigned long long ho = hash_byte0 + d.flat_off;
+        const char* fb = flat_base;
+        unsigned long long h = 0;
+        if (WIDEN && d.cast != kCastNone) {
+          switch (d.vec) {
+            case 16: h = widen_range<16, HASH>(d, fb, s, e, ho); break;
+            case 8: h = widen_range<8, HASH>(d, fb, s, e, ho); break;
+            case 4: h = widen_range<4, HASH>(d, fb, s, e, ho); break;
+            default: h = widen_range<2, HASH>(d, fb, s, e, ho); break;
+          }
+        } else {
+          switch (d.vec) {
+            case 16: h = scatter_range<16, HASH>(d, fb, s, e, ho); break;
+            case 8: h = scatter_range<8, HASH>(d, fb, s, e, ho); break;
+            case 4: h = scatter_range<4, HASH>(d, fb, s, e, ho); break;
+            case 2: h = scatter_range<2, HASH>(d, fb, s, e, ho); break;
+            default: h = scatter_range<1, HASH>(d, fb, s, e, ho); break;
+          }
+        }
+        if (HASH) add_per_wave(&hash_out[owner], h);
+      });
 }
 
 // ---------------------------------------------------------------------------
 // non-finite scan: count NaN and +-Inf elements per descriptor, read-only.
-// Same descriptors, work units and traversals as the gather; there is no
-// flat side (flat_off is unused) and nbytes/row_bytes/vec are the tensor's
-// own bytes. The element class travels in an array beside the descriptors,
-// so Desc::cast stays what parse_descs polices for gather and scatter.
+// Same descriptors, driver and traversal as the gather; there is no flat
+// side (flat_off is unused) and nbytes/row_bytes/vec are the tensor's own
+// bytes. The element class travels in an array beside the descriptors
+// (kScan* in desc_check.h), so Desc::cast stays a gather/scatter matter.
 // Classification is integer arithmetic on the loaded words, like the casts:
 // no dependence on the wave's float mode. The two "stored" classes count
 // what the save_dtype narrowing above will write: a finite f32 at or above
 // 65520 (0x477FF000) rounds to f16 inf, one at or above 0x7F7F8000 to bf16
 // inf.
 // ---------------------------------------------------------------------------
-
-constexpr uint32_t kScanF64 = 0;
-constexpr uint32_t kScanF32 = 1;
-constexpr uint32_t kScanF16 = 2;
-constexpr uint32_t kScanBF16 = 3;
-constexpr uint32_t kScanE5M2 = 4;
-constexpr uint32_t kScanE4M3FN = 5;
-constexpr uint32_t kScanFNUZ = 6;  // e4m3fnuz and e5m2fnuz: NaN is 0x80
-constexpr uint32_t kScanF32asF16 = 7;
-constexpr uint32_t kScanF32asBF16 = 8;
-constexpr uint32_t kScanClasses = 9;
-
-__device__ __host__ constexpr uint32_t scan_elem_size(uint32_t cls) {
-  return cls == kScanF64 ? 8u
-         : (cls == kScanF32 || cls >= kScanF32asF16) ? 4u
-         : (cls == kScanF16 || cls == kScanBF16) ? 2u
-                                                 : 1u;
-}
 
 // Classify the elements packed in one 32-bit word. A narrower load arrives
 // zero-extended, and an all-zero element is finite in every class, so the
@@ -794,51 +712,15 @@ __device__ inline void scan_vec(const char* p, uint32_t& nan, uint32_t& inf) {
   }
 }
 
-// Scan counterpart of process_range: [s, e) of the tensor's own bytes for
-// one work unit, the same three traversals, loads only.
+// Scan counterpart of gather_range: [s, e) of the tensor's own bytes for
+// one work unit, loads only.
 template <int VEC, uint32_t CLS>
 __device__ __forceinline__ void scan_range(const Desc& d, uint32_t s,
                                            uint32_t e, uint32_t& nan,
                                            uint32_t& inf) {
-  const uint32_t tid = threadIdx.x;
-  const uint32_t rb = d.row_bytes;
-  if (d.ndim == 0 || rb == d.nbytes) {
-    const char* src = d.tensor_base;
-#pragma unroll 4
-    for (uint32_t i = s + tid * VEC; i < e; i += kBlockThreads * VEC) {
-      scan_vec<VEC, CLS>(src + i, nan, inf);
-    }
-    return;
-  }
-  if (rb >= kWideRowBytes) {
-    // wide rows: rows sequential, lanes across columns
-    uint32_t row = s / rb;
-    uint32_t col = s - row * rb;
-    uint32_t off = s;
-    while (off < e) {
-      const char* src = d.tensor_base + row_offset(d, row) + col;
-      uint32_t n = min(rb - col, e - off);
-      for (uint32_t i = tid * VEC; i < n; i += kBlockThreads * VEC) {
-        scan_vec<VEC, CLS>(src + i, nan, inf);
-      }
-      off += n;
-      ++row;
-      col = 0;
-    }
-  } else {
-    // narrow rows: one lane per row
-    uint32_t first_row = s / rb;
-    uint32_t last_row = (e - 1) / rb;
-    for (uint32_t r = first_row + tid; r <= last_row; r += kBlockThreads) {
-      const char* src = d.tensor_base + row_offset(d, r);
-      uint32_t flat_pos = r * rb;
-      uint32_t lo = flat_pos < s ? (s - flat_pos) : 0;
-      uint32_t hi = (flat_pos + rb > e) ? (e - flat_pos) : rb;
-      for (uint32_t i = lo; i < hi; i += VEC) {
-        scan_vec<VEC, CLS>(src + i, nan, inf);
-      }
-    }
-  }
+  for_each_vec<VEC, 1, 4>(d, s, e, [&](unsigned long long, const char* p) {
+    scan_vec<VEC, CLS>(p, nan, inf);
+  });
 }
 
 // The class switch sits outside the traversal: the inner loops are
@@ -871,42 +753,26 @@ __global__ __launch_bounds__(kBlockThreads) void scan_kernel(
     const Desc* __restrict__ descs, const uint32_t* __restrict__ classes,
     int n, const unsigned long long* __restrict__ wu_prefix,
     unsigned long long total_wus, unsigned long long* __restrict__ counts) {
-  for (unsigned long long wu = blockIdx.x; wu < total_wus; wu += gridDim.x) {
-    // binary search: which tensor owns this work unit
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-      int mid = (lo + hi + 1) >> 1;
-      if (wu_prefix[mid] <= wu) lo = mid;
-      else hi = mid - 1;
-    }
-    const Desc d = descs[lo];
-    unsigned long long local_wu = wu - wu_prefix[lo];
-    uint32_t s = (uint32_t)(local_wu * kWorkUnitBytes);
-    uint32_t e = d.nbytes - s > kWorkUnitBytes ? s + kWorkUnitBytes : d.nbytes;
-    uint32_t nan = 0, inf = 0;
-    switch (classes[lo]) {
-      case kScanF64: scan_class<kScanF64>(d, s, e, nan, inf); break;
-      case kScanF32: scan_class<kScanF32>(d, s, e, nan, inf); break;
-      case kScanF16: scan_class<kScanF16>(d, s, e, nan, inf); break;
-      case kScanBF16: scan_class<kScanBF16>(d, s, e, nan, inf); break;
-      case kScanE5M2: scan_class<kScanE5M2>(d, s, e, nan, inf); break;
-      case kScanE4M3FN: scan_class<kScanE4M3FN>(d, s, e, nan, inf); break;
-      case kScanFNUZ: scan_class<kScanFNUZ>(d, s, e, nan, inf); break;
-      case kScanF32asF16:
-        scan_class<kScanF32asF16>(d, s, e, nan, inf);
-        break;
-      default: scan_class<kScanF32asBF16>(d, s, e, nan, inf); break;
-    }
-    // wave64 reduction, then one atomic per wave per work unit and counter
-    for (int delta = 32; delta > 0; delta >>= 1) {
-      nan += __shfl_down(nan, delta, 64);
-      inf += __shfl_down(inf, delta, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      if (nan != 0) atomicAdd(&counts[2 * lo], (unsigned long long)nan);
-      if (inf != 0) atomicAdd(&counts[2 * lo + 1], (unsigned long long)inf);
-    }
-  }
+  for_each_work_unit(
+      descs, n, wu_prefix, total_wus,
+      [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
+        uint32_t nan = 0, inf = 0;
+        switch (classes[owner]) {
+          case kScanF64: scan_class<kScanF64>(d, s, e, nan, inf); break;
+          case kScanF32: scan_class<kScanF32>(d, s, e, nan, inf); break;
+          case kScanF16: scan_class<kScanF16>(d, s, e, nan, inf); break;
+          case kScanBF16: scan_class<kScanBF16>(d, s, e, nan, inf); break;
+          case kScanE5M2: scan_class<kScanE5M2>(d, s, e, nan, inf); break;
+          case kScanE4M3FN: scan_class<kScanE4M3FN>(d, s, e, nan, inf); break;
+          case kScanFNUZ: scan_class<kScanFNUZ>(d, s, e, nan, inf); break;
+          case kScanF32asF16:
+            scan_class<kScanF32asF16>(d, s, e, nan, inf);
+            break;
+          default: scan_class<kScanF32asBF16>(d, s, e, nan, inf); break;
+        }
+        add_per_wave(&counts[2 * owner], nan);
+        add_per_wave(&counts[2 * owner + 1], inf);
+      });
 }
 
 // ---------------------------------------------------------------------------
@@ -974,152 +840,29 @@ void chain_after(hipStream_t side, uintptr_t producer_stream, int device) {
   }
 }
 
-// flat desc rows from python: 19 u64 each (see ops/staging.py)
-constexpr int kRowInts = 19;
-
-// `widen`: the caller is unpack_h2d, which takes the widening codes (and
-// not the narrowing ones); everything else takes codes 0..2 only.
-std::vector<Desc> parse_descs(const std::vector<unsigned long long>& flat,
-                              int n, bool widen = false) {
-  if ((int)flat.size() != n * kRowInts) {
-    throw std::runtime_error("bad descriptor array length");
-  }
-  std::vector<Desc> descs(n);
-  for (int i = 0; i < n; ++i) {
-    const unsigned long long* r = flat.data() + i * kRowInts;
-    Desc& d = descs[i];
-    d.tensor_base = reinterpret_cast<const char*>(r[0]);
-    d.flat_off = r[1];
-    if (r[2] >= (1ull << 32)) {
-      throw std::runtime_error(
-          "tensor too large for pack kernel (>=4GB); chunk it upstream");
-    }
-    d.nbytes = (uint32_t)r[2];
-    d.row_bytes = (uint32_t)r[3];
-    d.vec = (uint32_t)r[4];
-    d.ndim = (uint32_t)r[5];
-    for (int k = 0; k < kMaxDims; ++k) {
-      d.sizes[k] = (uint32_t)r[6 + k];
-      d.strides[k] = (long long)r[12 + k];
-    }
-    if (d.ndim > (uint32_t)kMaxDims) {
-      throw std::runtime_error("too many outer dims");
-    }
-    if (r[18] > kCastF16toF32) {
-      throw std::runtime_error("unknown cast code in descriptor");
-    }
-    if (!widen && r[18] > kCastF16) {
-      throw std::runtime_error(
-          "widening cast descriptors are scatter-only (unpack_h2d)");
-    }
-    if (widen && r[18] != kCastNone && r[18] <= kCastF16) {
-      throw std::runtime_error(
-          "unpack_h2d does not support narrowing cast descriptors");
-    }
-    d.cast = (uint32_t)r[18];
-    if (d.cast != kCastNone && d.nbytes != 0) {
-      // the cast lanes move 2*vec bytes on the tensor side and vec bytes
-      // on the flat side, each as naturally aligned vector accesses:
-      // refuse a descriptor whose layout would misalign or overrun them
-      const uint32_t v = d.vec;
-      if (v != 16 && v != 8 && v != 4 && v != 2) {
-        throw std::runtime_error("cast descriptor: vec must be 16/8/4/2");
-      }
-      if (d.row_bytes == 0 || d.row_bytes % v != 0 ||
-          d.nbytes % d.row_bytes != 0) {
-        throw std::runtime_error("cast descriptor: row_bytes/vec mismatch");
-      }
-      const unsigned long long src_align = v == 16 ? 16 : 2ull * v;
-      bool ok = (r[0] % src_align) == 0;
-      for (uint32_t k = 0; k < d.ndim; ++k) {
-        ok = ok && ((unsigned long long)d.strides[k] % src_align) == 0;
-      }
-      if (!ok) {
-        throw std::runtime_error(
-            "cast descriptor: source not aligned for its vec");
-      }
-    }
-  }
-  return descs;
-}
-
-// unpack_h2d's extra checks, all before the GPU is touched: every flat
-// range lies inside the payload, and every vector access the kernel will
-// make on either side is naturally aligned.
-void check_unpack_descs(const std::vector<Desc>& descs, uintptr_t slab_ptr,
-                        uintptr_t pinned_ptr, unsigned long long total_bytes,
-                        unsigned long long hash_byte0) {
-  if (hash_byte0 % 8 != 0) {
-    throw std::runtime_error("unpack_h2d: hash_byte0 must be 8-aligned");
-  }
-  if (slab_ptr % 16 != 0) {
-    throw std::runtime_error("unpack_h2d: slab must be 16-aligned");
-  }
-  for (const Desc& d : descs) {
-    if (d.nbytes == 0) continue;
-    // u32 indices inside the kernel step by at most 4 KiB past nbytes
-    if (d.nbytes > 0xFFFFFFFFu - kWorkUnitBytes) {
-      throw std::runtime_error(
-          "unpack_h2d: tensor too large (>= 4 GiB - 64 KiB stored)");
-    }
-    if (d.flat_off > total_bytes || d.nbytes > total_bytes - d.flat_off) {
-      throw std::runtime_error("unpack_h2d: descriptor outside the payload");
-    }
-    const uint32_t v = d.vec;
-    if (v != 16 && v != 8 && v != 4 && v != 2 && v != 1) {
-      throw std::runtime_error("unpack_h2d: vec must be 16/8/4/2/1");
-    }
-    if (d.row_bytes == 0 || d.row_bytes % v != 0 ||
-        d.nbytes % d.row_bytes != 0) {
-      throw std::runtime_error("unpack_h2d: row_bytes/vec mismatch");
-    }
-    if ((pinned_ptr + d.flat_off) % v != 0) {
-      throw std::runtime_error(
-          "unpack_h2d: flat address not aligned for its vec");
-    }
-    if (d.cast == kCastNone) {
-      // widen descriptors had their tensor side checked by parse_descs
-      bool ok = reinterpret_cast<uintptr_t>(d.tensor_base) % v == 0;
-      for (uint32_t k = 0; k < d.ndim; ++k) {
-        ok = ok && ((unsigned long long)d.strides[k] % v) == 0;
-      }
-      if (!ok) {
-        throw std::runtime_error(
-            "unpack_h2d: tensor not aligned for its vec");
-      }
-    }
-  }
-}
-
+// One launcher for the three copy entry points. `kind` picks the rules
+// check_descs applies and the kernel family: Gather runs pack_kernel on
+// the D2H side stream, Scatter and Unpack run unpack_kernel on the H2D
+// one (Scatter never casts or hashes).
 long long launch_pack(const std::vector<unsigned long long>& flat, int n,
-                      uintptr_t slab_ptr, uintptr_t pinned_ptr,
+                      DescKind kind, uintptr_t slab_ptr, uintptr_t pinned_ptr,
                       unsigned long long total_bytes, uintptr_t producer_stream,
-                      int device, bool gather, uintptr_t hash_out_ptr,
-                      bool unpack = false, unsigned long long hash_byte0 = 0) {
-  // `unpack` (scatter only) selects unpack_kernel: widening descriptors
-  // and the fused psum64 at file offset hash_byte0 + flat_off
-  std::vector<Desc> descs = parse_descs(flat, n, unpack);
+                      int device, uintptr_t hash_out_ptr = 0,
+                      unsigned long long hash_byte0 = 0) {
+  // everything is refused here, before the GPU is touched
+  const std::vector<Desc> descs = parse_descs(flat, n);
+  const FlatSide flat_side{slab_ptr, pinned_ptr, total_bytes, hash_byte0};
+  check_descs(descs, kind, &flat_side);
+  const bool gather = kind == DescKind::Gather;
   bool any_cast = false;
   for (const Desc& d : descs) any_cast = any_cast || d.cast != kCastNone;
-  if (any_cast && !gather && !unpack) {
-    // scatter_h2d stays a plain byte scatter; refuse before touching the GPU
-    throw std::runtime_error(
-        "scatter_h2d does not support cast descriptors (gather only)");
-  }
-  if (unpack) check_unpack_descs(descs, slab_ptr, pinned_ptr, total_bytes,
-                                 hash_byte0);
 
   HIP_CHECK(hipSetDevice(device));
   DeviceCtx& ctx = get_ctx(device);
   hipStream_t stream = gather ? ctx.d2h_stream : ctx.h2d_stream;
 
-  std::vector<unsigned long long> wu_prefix(n + 1, 0);
-  for (int i = 0; i < n; ++i) {
-    unsigned long long wus =
-        (descs[i].nbytes + kWorkUnitBytes - 1) / kWorkUnitBytes;
-    wu_prefix[i + 1] = wu_prefix[i] + wus;
-  }
-  unsigned long long total_wus = wu_prefix[n];
+  const std::vector<unsigned long long> wu_prefix = wu_prefix_of(descs);
+  const unsigned long long total_wus = wu_prefix[n];
 
   // flat side: device slab if provided, else the pinned host buffer
   // (device-addressable) for direct PCIe writes/reads
@@ -1137,21 +880,14 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
 
   chain_after(stream, producer_stream, device);
 
-  // stage descriptors + prefix sums in one device allocation
-  size_t desc_bytes = sizeof(Desc) * n;
-  size_t prefix_bytes = sizeof(unsigned long long) * (n + 1);
-  std::vector<char> staging(desc_bytes + prefix_bytes);
-  memcpy(staging.data(), descs.data(), desc_bytes);
-  memcpy(staging.data() + desc_bytes, wu_prefix.data(), prefix_bytes);
+  // descriptors + prefix sums in one device allocation, one copy
+  LaunchTables tables(descs, wu_prefix);
   void* scratch = nullptr;
-  HIP_CHECK(hipMallocAsync(&scratch, staging.size(), stream));
-  HIP_CHECK(hipMemcpyAsync(scratch, staging.data(), staging.size(),
+  HIP_CHECK(hipMallocAsync(&scratch, tables.host.size(), stream));
+  HIP_CHECK(hipMemcpyAsync(scratch, tables.host.data(), tables.host.size(),
                            hipMemcpyHostToDevice, stream));
-
-  const Desc* d_descs = reinterpret_cast<const Desc*>(scratch);
-  const unsigned long long* d_prefix =
-      reinterpret_cast<const unsigned long long*>(
-          reinterpret_cast<char*>(scratch) + desc_bytes);
+  const Desc* d_descs = tables.descs(scratch);
+  const unsigned long long* d_prefix = tables.prefix(scratch);
 
   if (!gather && slab_ptr != 0) {
     // restore via slab: H2D copy first, then scatter out of the slab
@@ -1166,18 +902,20 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
   // gathers at HBM speed and wants the chip filled (all 8 XCDs). The
   // restore kernel's reads of pinned memory behave the same way: 128-256
   // workgroups reach the link rate, 1024+ lose a few percent.
-  bool direct_mode = (slab_ptr == 0);
-  unsigned long long grid_cap = direct_mode ? 256ull : 16384ull;
-  if (const char* env = getenv("TSAMD_PACK_GRID")) {
-    long v = atol(env);
-    if (v > 0) grid_cap = (unsigned long long)v;
-  }
-  unsigned int grid = (unsigned int)std::min<unsigned long long>(
-      total_wus == 0 ? 1 : total_wus, grid_cap);
+  const bool direct_mode = (slab_ptr == 0);
+  const unsigned int grid = grid_for(total_wus, direct_mode ? 256ull : 16384ull,
+                                     getenv("TSAMD_PACK_GRID"));
   unsigned long long* hash_out =
       reinterpret_cast<unsigned long long*>(hash_out_ptr);
-  if (unpack) {
-    const bool hash = hash_out != nullptr;
+  const bool hash = hash_out != nullptr;
+  if (gather) {
+    auto kernel = any_cast ? (hash ? pack_kernel<true, true>
+                                   : pack_kernel<false, true>)
+                           : (hash ? pack_kernel<true, false>
+                                   : pack_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
+                       d_descs, n, d_prefix, total_wus, flat_base, hash_out);
+  } else {
     auto kernel = any_cast ? (hash ? unpack_kernel<true, true>
                                    : unpack_kernel<false, true>)
                            : (hash ? unpack_kernel<true, false>
@@ -1186,26 +924,6 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
                        d_descs, n, d_prefix, total_wus,
                        static_cast<const char*>(flat_base), hash_out,
                        hash_byte0);
-  } else if (any_cast && hash_out != nullptr) {
-    hipLaunchKernelGGL((pack_kernel<true, true, true>), dim3(grid),
-                       dim3(kBlockThreads), 0, stream, d_descs, n, d_prefix,
-                       total_wus, flat_base, hash_out);
-  } else if (any_cast) {
-    hipLaunchKernelGGL((pack_kernel<true, false, true>), dim3(grid),
-                       dim3(kBlockThreads), 0, stream, d_descs, n, d_prefix,
-                       total_wus, flat_base, nullptr);
-  } else if (gather && hash_out != nullptr) {
-    hipLaunchKernelGGL((pack_kernel<true, true>), dim3(grid),
-                       dim3(kBlockThreads), 0, stream, d_descs, n, d_prefix,
-                       total_wus, flat_base, hash_out);
-  } else if (gather) {
-    hipLaunchKernelGGL((pack_kernel<true, false>), dim3(grid),
-                       dim3(kBlockThreads), 0, stream, d_descs, n, d_prefix,
-                       total_wus, flat_base, nullptr);
-  } else {
-    hipLaunchKernelGGL((pack_kernel<false, false>), dim3(grid),
-                       dim3(kBlockThreads), 0, stream, d_descs, n, d_prefix,
-                       total_wus, flat_base, nullptr);
   }
   HIP_CHECK(hipGetLastError());
 
@@ -1220,9 +938,9 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
   hipEvent_t ev;
   HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   HIP_CHECK(hipEventRecord(ev, stream));
-  return register_op(ev, device, nullptr, std::move(staging));
+  // the host image must outlive the copy that reads it
+  return register_op(ev, device, nullptr, std::move(tables.host));
 }
-
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1244,36 +962,21 @@ static long long d2h_copy(uintptr_t src, uintptr_t dst_pinned,
   return register_op(ev, device, nullptr, {});
 }
 
-static long long h2d_copy(uintptr_t src_pinned, uintptr_t dst,
-                          unsigned long long nbytes, uintptr_t producer_stream,
-                          int device) {
-  HIP_CHECK(hipSetDevice(device));
-  DeviceCtx& ctx = get_ctx(device);
-  chain_after(ctx.h2d_stream, producer_stream, device);
-  HIP_CHECK(hipMemcpyAsync(reinterpret_cast<void*>(dst),
-                           reinterpret_cast<void*>(src_pinned), nbytes,
-                           hipMemcpyHostToDevice, ctx.h2d_stream));
-  hipEvent_t ev;
-  HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  HIP_CHECK(hipEventRecord(ev, ctx.h2d_stream));
-  return register_op(ev, device, nullptr, {});
-}
-
 static long long pack_d2h(const std::vector<unsigned long long>& flat, int n,
                           uintptr_t slab_ptr, uintptr_t pinned_ptr,
                           unsigned long long total_bytes,
                           uintptr_t producer_stream, int device,
                           uintptr_t hash_out_ptr = 0) {
-  return launch_pack(flat, n, slab_ptr, pinned_ptr, total_bytes,
-                     producer_stream, device, /*gather=*/true, hash_out_ptr);
+  return launch_pack(flat, n, DescKind::Gather, slab_ptr, pinned_ptr,
+                     total_bytes, producer_stream, device, hash_out_ptr);
 }
 
 static long long scatter_h2d(const std::vector<unsigned long long>& flat, int n,
                              uintptr_t slab_ptr, uintptr_t pinned_ptr,
                              unsigned long long total_bytes,
                              uintptr_t producer_stream, int device) {
-  return launch_pack(flat, n, slab_ptr, pinned_ptr, total_bytes,
-                     producer_stream, device, /*gather=*/false, 0);
+  return launch_pack(flat, n, DescKind::Scatter, slab_ptr, pinned_ptr,
+                     total_bytes, producer_stream, device);
 }
 
 static long long unpack_h2d(const std::vector<unsigned long long>& flat,
@@ -1282,9 +985,9 @@ static long long unpack_h2d(const std::vector<unsigned long long>& flat,
                             uintptr_t producer_stream, int device,
                             uintptr_t hash_out_ptr = 0,
                             unsigned long long hash_byte0 = 0) {
-  return launch_pack(flat, n, slab_ptr, pinned_ptr, total_bytes,
-                     producer_stream, device, /*gather=*/false, hash_out_ptr,
-                     /*unpack=*/true, hash_byte0);
+  return launch_pack(flat, n, DescKind::Unpack, slab_ptr, pinned_ptr,
+                     total_bytes, producer_stream, device, hash_out_ptr,
+                     hash_byte0);
 }
 
 // ---------------------------------------------------------------------------
@@ -1378,98 +1081,29 @@ static unsigned long long psum64_dev(uintptr_t ptr, unsigned long long nbytes,
 // Inf elements of each descriptor.
 // ---------------------------------------------------------------------------
 
-namespace {
-
-// All before the GPU is touched: every vector load the kernel will make is
-// naturally aligned, covers whole elements and stays inside the rows the
-// descriptor names, and no u32 index can wrap.
-void check_scan_descs(const std::vector<Desc>& descs,
-                      const std::vector<uint32_t>& classes) {
-  if (classes.size() != descs.size()) {
-    throw std::runtime_error("scan_nonfinite: one class code per descriptor");
-  }
-  for (size_t i = 0; i < descs.size(); ++i) {
-    const Desc& d = descs[i];
-    if (classes[i] >= kScanClasses) {
-      throw std::runtime_error("scan_nonfinite: unknown element class");
-    }
-    if (d.cast != kCastNone) {
-      throw std::runtime_error("scan_nonfinite: cast descriptors not allowed");
-    }
-    if (d.nbytes == 0) continue;
-    // u32 indices inside the kernel step by at most 4 KiB past nbytes;
-    // 2^32 - 64 KiB itself is allowed (ops/staging.py's _SCAN_MAX_BYTES)
-    if (d.nbytes > 0xFFFFFFFFu - kWorkUnitBytes + 1u) {
-      throw std::runtime_error(
-          "scan_nonfinite: tensor too large (> 4 GiB - 64 KiB)");
-    }
-    const uint32_t v = d.vec;
-    if (v != 16 && v != 8 && v != 4 && v != 2 && v != 1) {
-      throw std::runtime_error("scan_nonfinite: vec must be 16/8/4/2/1");
-    }
-    if (v < scan_elem_size(classes[i])) {
-      throw std::runtime_error("scan_nonfinite: vec below the element size");
-    }
-    if (d.row_bytes == 0 || d.row_bytes % v != 0 ||
-        d.nbytes % d.row_bytes != 0) {
-      throw std::runtime_error("scan_nonfinite: row_bytes/vec mismatch");
-    }
-    bool ok = reinterpret_cast<uintptr_t>(d.tensor_base) % v == 0;
-    unsigned long long rows = 1;
-    for (uint32_t k = 0; k < d.ndim; ++k) {
-      ok = ok && ((unsigned long long)d.strides[k] % v) == 0;
-      ok = ok && d.strides[k] >= 0 && d.sizes[k] != 0;
-      rows *= d.sizes[k];
-    }
-    if (!ok) {
-      throw std::runtime_error(
-          "scan_nonfinite: tensor not aligned for its vec");
-    }
-    if (d.ndim != 0 && rows * d.row_bytes != d.nbytes) {
-      throw std::runtime_error("scan_nonfinite: sizes do not cover nbytes");
-    }
-  }
-}
-
-}  // namespace
-
 static std::vector<unsigned long long> scan_nonfinite(
     const std::vector<unsigned long long>& flat,
     const std::vector<uint32_t>& classes, int n, uintptr_t producer_stream,
     int device) {
-  std::vector<Desc> descs = parse_descs(flat, n);
-  check_scan_descs(descs, classes);
+  // refused before the GPU is touched: every vector load the kernel will
+  // make is naturally aligned, covers whole elements and stays inside the
+  // rows the descriptor names
+  const std::vector<Desc> descs = parse_descs(flat, n);
+  check_descs(descs, DescKind::Scan, nullptr, &classes);
   std::vector<unsigned long long> counts(2 * (size_t)n, 0);
 
-  std::vector<unsigned long long> wu_prefix(n + 1, 0);
-  for (int i = 0; i < n; ++i) {
-    unsigned long long wus =
-        (descs[i].nbytes + kWorkUnitBytes - 1) / kWorkUnitBytes;
-    wu_prefix[i + 1] = wu_prefix[i] + wus;
-  }
+  const std::vector<unsigned long long> wu_prefix = wu_prefix_of(descs);
   const unsigned long long total_wus = wu_prefix[n];
   if (total_wus == 0) return counts;
 
-  // one device allocation: counters | descriptors | prefix sums | classes
+  // one device allocation: descriptors | prefix sums | classes | counters
+  const LaunchTables tables(descs, wu_prefix, classes.data(),
+                            sizeof(uint32_t) * n);
   const size_t count_bytes = sizeof(unsigned long long) * 2 * n;
-  const size_t desc_bytes = sizeof(Desc) * n;
-  const size_t prefix_bytes = sizeof(unsigned long long) * (n + 1);
-  const size_t class_bytes = sizeof(uint32_t) * n;
-  static_assert(sizeof(Desc) % 8 == 0, "prefix sums must stay 8-aligned");
-  std::vector<char> staging(desc_bytes + prefix_bytes + class_bytes);
-  memcpy(staging.data(), descs.data(), desc_bytes);
-  memcpy(staging.data() + desc_bytes, wu_prefix.data(), prefix_bytes);
-  memcpy(staging.data() + desc_bytes + prefix_bytes, classes.data(),
-         class_bytes);
 
   // HBM-bound read: fill the chip like the slab-mode gather does
-  unsigned long long grid_cap = 16384ull;
-  if (const char* env = getenv("TSAMD_PACK_GRID")) {
-    long v = atol(env);
-    if (v > 0) grid_cap = (unsigned long long)v;
-  }
   const unsigned int grid =
-      (unsigned int)std::min<unsigned long long>(total_wus, grid_cap);
+      grid_for(total_wus, 16384ull, getenv("TSAMD_PACK_GRID"));
 
   py::gil_scoped_release release;
   HIP_CHECK(hipSetDevice(device));
@@ -1478,26 +1112,22 @@ static std::vector<unsigned long long> scan_nonfinite(
   chain_after(stream, producer_stream, device);
 
   void* scratch = nullptr;
-  HIP_CHECK(hipMallocAsync(&scratch, count_bytes + staging.size(), stream));
-  char* base = reinterpret_cast<char*>(scratch);
-  unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(base);
-  const Desc* d_descs = reinterpret_cast<const Desc*>(base + count_bytes);
-  const unsigned long long* d_prefix =
-      reinterpret_cast<const unsigned long long*>(base + count_bytes +
-                                                  desc_bytes);
-  const uint32_t* d_classes = reinterpret_cast<const uint32_t*>(
-      base + count_bytes + desc_bytes + prefix_bytes);
+  HIP_CHECK(hipMallocAsync(&scratch, tables.host.size() + count_bytes, stream));
+  unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(
+      reinterpret_cast<char*>(scratch) + tables.host.size());
 
   // enqueue everything, then synchronise whatever happened: the host
   // buffers above must outlive the copies that read and write them
   hipError_t err = hipMemsetAsync(d_counts, 0, count_bytes, stream);
   if (err == hipSuccess) {
-    err = hipMemcpyAsync(base + count_bytes, staging.data(), staging.size(),
+    err = hipMemcpyAsync(scratch, tables.host.data(), tables.host.size(),
                          hipMemcpyHostToDevice, stream);
   }
   if (err == hipSuccess) {
     hipLaunchKernelGGL(scan_kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
-                       d_descs, d_classes, n, d_prefix, total_wus, d_counts);
+                       tables.descs(scratch),
+                       static_cast<const uint32_t*>(tables.extra(scratch)), n,
+                       tables.prefix(scratch), total_wus, d_counts);
     err = hipGetLastError();
   }
   if (err == hipSuccess) {
@@ -1688,7 +1318,6 @@ static void managed_prefetch(uintptr_t ptr, unsigned long long nbytes,
 PYBIND11_MODULE(_csnap, m) {
   m.doc() = "torchsnapshot_amd HIP staging engine (gfx950)";
   m.def("d2h_copy", &d2h_copy, "async D2H copy on the side stream");
-  m.def("h2d_copy", &h2d_copy, "async H2D copy on the side stream");
   m.def("pack_d2h", &pack_d2h,
         "gather-pack tensors into a slab and copy it to pinned host memory",
         py::arg("flat"), py::arg("n"), py::arg("slab_ptr"),
@@ -1718,7 +1347,8 @@ PYBIND11_MODULE(_csnap, m) {
         "(blocking); returns [nan_0, inf_0, nan_1, inf_1, ...]",
         py::arg("flat"), py::arg("classes"), py::arg("n"),
         py::arg("producer_stream"), py::arg("device"));
-  m.def("file_write", &file_write,
+  m.def("file_write", &::file_write,  // not tsamd::file_write
+       
         "write a buffer to a file (GIL released); reuse=True overwrites an "
         "existing file of >= 1 MiB payload in place instead of truncating",
         py::arg("path"), py::arg("buf"), py::arg("fsync") = false,

@@ -13,7 +13,7 @@ HIP data plane for gfx950:
   packed contiguously (256 B aligned each) either into a device slab that
   is then moved by a single SDMA copy, or directly into pinned host memory
   over PCIe (mode knob; both paths are implemented in
-  ops/hip/staging_kernels.hip).
+  ops/hip/staging.hip).
 
 Failure policy: if a CUDA/HIP tensor must be staged and the compiled
 extension is missing, we raise — a silent eager fallback would invalidate
@@ -151,6 +151,36 @@ def widen_code(stored: torch.dtype, target: torch.dtype) -> int:
     return code
 
 
+def _layout_rows(
+    sizes: List[int],
+    strides: List[int],
+    src_esz: int,
+    flat_esz: int,
+    data_ptr: int,
+) -> Tuple[int, List[int], List[int], int]:
+    """Rows of a collapsed element-unit layout, as every descriptor states
+    them: ``(row_bytes, outer_sizes, outer_strides_b, src_align)``.
+
+    ``row_bytes`` is the innermost contiguous run in flat-side bytes
+    (``flat_esz`` per element; it differs from ``src_esz`` only under a
+    cast), the outer strides are tensor-side bytes, and ``src_align`` is the
+    largest power of two up to 16 that divides the base address and every
+    outer stride (a stride of 0 divides by anything). Each builder derives
+    its own vec from these and keeps its own refusals."""
+    src_align = math.gcd(16, data_ptr)
+    if len(sizes) == 1 and strides[0] == 1:
+        return sizes[0] * flat_esz, [], [], src_align  # contiguous: one row
+    if strides[-1] == 1:
+        row_elems, n_outer = sizes[-1], len(sizes) - 1
+    else:
+        # innermost dim itself strided: rows of one element
+        row_elems, n_outer = 1, len(sizes)
+    outer_strides_b = [st * src_esz for st in strides[:n_outer]]
+    for st in outer_strides_b:
+        src_align = math.gcd(src_align, st if st else 16)
+    return row_elems * flat_esz, sizes[:n_outer], outer_strides_b, src_align
+
+
 def build_pack_items(
     tensors: Sequence[torch.Tensor],
     out_dtypes: Optional[Sequence[Optional[torch.dtype]]] = None,
@@ -181,21 +211,10 @@ def build_pack_items(
             items.append(PackItem(t.data_ptr(), off, 0, 0, [], [], 1))
             offsets.append(off)
             continue
-        if strides and strides[-1] == 1:
-            row_elems = sizes[-1]
-            outer_sizes = sizes[:-1]
-            outer_strides_b = [st * esz for st in strides[:-1]]
-        else:
-            # innermost dim itself strided: rows of one element
-            row_elems = 1
-            outer_sizes = sizes
-            outer_strides_b = [st * esz for st in strides]
-        row_bytes = row_elems * esz
-        vec = 16
-        vec = math.gcd(vec, row_bytes)
-        vec = math.gcd(vec, t.data_ptr())
-        for st in outer_strides_b:
-            vec = math.gcd(vec, st if st else 16)
+        row_bytes, outer_sizes, outer_strides_b, src_align = _layout_rows(
+            sizes, strides, esz, esz, t.data_ptr()
+        )
+        vec = math.gcd(row_bytes, src_align)
         items.append(
             PackItem(
                 src_ptr=t.data_ptr(),
@@ -224,18 +243,9 @@ def _build_cast_item(
     src_esz = t.element_size()
     dst_esz = out_dtype.itemsize
     sizes, strides = collapse_layout(t)
-    if strides[-1] == 1:
-        row_elems = sizes[-1]
-        outer_sizes = sizes[:-1]
-        outer_strides_b = [st * src_esz for st in strides[:-1]]
-    else:
-        row_elems = 1
-        outer_sizes = sizes
-        outer_strides_b = [st * src_esz for st in strides]
-    row_bytes = row_elems * dst_esz
-    src_align = math.gcd(16, t.data_ptr())
-    for st in outer_strides_b:
-        src_align = math.gcd(src_align, st if st else 16)
+    row_bytes, outer_sizes, outer_strides_b, src_align = _layout_rows(
+        sizes, strides, src_esz, dst_esz, t.data_ptr()
+    )
     if src_align < src_esz:
         raise ValueError(
             f"cannot cast-stage a {t.dtype} tensor whose address or strides "
@@ -286,9 +296,11 @@ def build_scatter_items(
     return items
 
 
-# u32 indices inside the scatter kernel step up to 4 KiB past a tensor's
-# stored size; the extension refuses anything closer to 4 GiB than this
-_SCATTER_MAX_STORED_BYTES = 2**32 - 2**16
+# The extension's cap on one descriptor's flat-side bytes (gather, scatter
+# and scan alike; kMaxDescBytes in ops/hip/desc_check.h): u32 indices inside
+# the kernels step up to 4 KiB past a tensor's size, so anything closer to
+# 4 GiB than one 64 KiB work unit is refused on the host.
+_KERNEL_MAX_BYTES = 2**32 - 2**16
 
 
 def scatter_plan(
@@ -326,7 +338,7 @@ def _scatter_layout_plan(
     n_outer = len(sizes) - 1 if strides[-1] == 1 else len(sizes)
     if n_outer > 6:
         return None
-    if target.numel() * stored_dtype.itemsize >= _SCATTER_MAX_STORED_BYTES:
+    if target.numel() * stored_dtype.itemsize >= _KERNEL_MAX_BYTES:
         return None
     # torch strides are whole elements, so the base address decides whether
     # every element is aligned
@@ -388,10 +400,6 @@ _SCAN_STORED_CLASSES = {
     CAST_F32_TO_BF16: SCAN_F32_AS_BF16,
 }
 
-# u32 indices inside the scan kernel step up to 4 KiB past a tensor's size;
-# the extension accepts this many bytes and refuses anything larger
-_SCAN_MAX_BYTES = 2**32 - 2**16
-
 
 def collapse_layout_by_stride(t: torch.Tensor) -> Tuple[List[int], List[int]]:
     """collapse_layout() for consumers that do not care about element order
@@ -443,27 +451,18 @@ def _scan_view(t: torch.Tensor) -> Optional[torch.Tensor]:
 
 
 def _build_scan_item(t: torch.Tensor) -> Optional[PackItem]:
-    """Descriptor of one real float view of at most _SCAN_MAX_BYTES, or None
-    when the kernel cannot take it."""
+    """Descriptor of one real float view of at most _KERNEL_MAX_BYTES, or
+    None when the kernel cannot take it."""
     esz = t.element_size()
     if t.is_neg():
         return None
     sizes, strides = collapse_layout_by_stride(t)
-    if strides[-1] == 1:
-        row_elems = sizes[-1]
-        outer_sizes = sizes[:-1]
-        outer_strides_b = [st * esz for st in strides[:-1]]
-    else:
-        row_elems = 1
-        outer_sizes = sizes
-        outer_strides_b = [st * esz for st in strides]
+    row_bytes, outer_sizes, outer_strides_b, src_align = _layout_rows(
+        sizes, strides, esz, esz, t.data_ptr()
+    )
     if len(outer_sizes) > 6:
         return None
-    row_bytes = row_elems * esz
-    vec = math.gcd(16, row_bytes)
-    vec = math.gcd(vec, t.data_ptr())
-    for st in outer_strides_b:
-        vec = math.gcd(vec, st if st else 16)
+    vec = math.gcd(row_bytes, src_align)
     if vec < esz:
         return None  # storage offset splits an element
     return PackItem(
@@ -522,12 +521,12 @@ def _split_for_scan(t: torch.Tensor) -> Optional[List[torch.Tensor]]:
     if t.numel() == 0:
         return []
     nbytes = t.numel() * t.element_size()
-    if nbytes <= _SCAN_MAX_BYTES:
+    if nbytes <= _KERNEL_MAX_BYTES:
         return [t]
     if t.dim() == 0:
         return None
     row_bytes = nbytes // t.shape[0]
-    max_bytes = min(knobs.get_max_chunk_size_bytes(), _SCAN_MAX_BYTES)
+    max_bytes = min(knobs.get_max_chunk_size_bytes(), _KERNEL_MAX_BYTES)
     if row_bytes > max_bytes:
         return None
     rows = max_bytes // row_bytes
