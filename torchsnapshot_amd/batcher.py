@@ -22,18 +22,23 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import knobs
+from . import integrity, knobs
 from .io_types import (
-    BufferConsumer,
     BufferStager,
     BufferType,
     ReadReq,
     StageContext,
     WriteReq,
 )
+from .io_preparers.pinned_read import PinnedReadConsumer, payload_to_device
 from .io_preparers.tensor import TensorBufferStager
-from .ops.staging import ALIGN, build_pack_items, get_pinned_pool, get_staging_engine
-from .serialization import SERIALIZER_BUFFER
+from .ops.staging import (
+    ALIGN,
+    HIP_EXT_AVAILABLE,
+    build_pack_items,
+    get_staging_engine,
+)
+from .serialization import SERIALIZER_BUFFER, tensor_as_memoryview
 
 
 def _is_batchable(req: WriteReq) -> bool:
@@ -129,11 +134,6 @@ class BatchedBufferStager(BufferStager):
         self.total_bytes = total_bytes
         self.is_async_snapshot = is_async_snapshot
         self._staged_batch = None
-        self._pinned_block = None
-        self.precomputed_checksum = None
-        # [(start, end, "psum64:<hex>")] per member, recorded so restore
-        # can verify byte-range/merged-span reads of this slab
-        self.member_checksums = None
 
     def get_staging_cost_bytes(self) -> int:
         return self.total_bytes
@@ -146,8 +146,6 @@ class BatchedBufferStager(BufferStager):
         return await loop.run_in_executor(ctx.executor, self._stage_cpu)
 
     def _stage_device(self) -> BufferType:
-        from . import integrity
-
         engine = get_staging_engine(self.tensors[0].device)
         ck = integrity.checksumming_enabled()
         batch = engine.stage(
@@ -157,10 +155,11 @@ class BatchedBufferStager(BufferStager):
         if ck and batch.checksums is not None:
             # padding is zeroed, so the slab-file checksum is the sum of
             # the per-member device checksums
-            total = sum(batch.checksums) % (1 << 64)
-            self.precomputed_checksum = "psum64:" + format(total, "016x")
+            self.precomputed_checksum = integrity.format_psum64(
+                sum(batch.checksums)
+            )
             self.member_checksums = [
-                (off, off + n, "psum64:" + format(v % (1 << 64), "016x"))
+                (off, off + n, integrity.format_psum64(v))
                 for off, n, v in zip(
                     batch.offsets, batch.nbytes_list, batch.checksums
                 )
@@ -169,13 +168,9 @@ class BatchedBufferStager(BufferStager):
         return batch.slab_memoryview()
 
     def _stage_cpu(self) -> BufferType:
-        from . import integrity
-
         items, offsets, total = build_pack_items(self.tensors, self.out_dtypes)
         slab = bytearray(total)
         mv = memoryview(slab)
-        from .serialization import tensor_as_memoryview
-
         ck = integrity.checksumming_enabled()
         members = []
         for t, off, out_dtype in zip(self.tensors, offsets, self.out_dtypes):
@@ -196,10 +191,9 @@ class BatchedBufferStager(BufferStager):
                 )
         if ck:
             self.member_checksums = members
-            total_ck = sum(
-                int(v[len("psum64:"):], 16) for _, _, v in members
-            ) % (1 << 64)
-            self.precomputed_checksum = "psum64:" + format(total_ck, "016x")
+            self.precomputed_checksum = integrity.format_psum64(
+                sum(integrity.parse_psum64(v) for _, _, v in members)
+            )
         return mv
 
     def release_buffer(self) -> None:
@@ -270,25 +264,10 @@ def _make_span(
     )
 
 
-class BatchedBufferConsumer(BufferConsumer):
+class BatchedBufferConsumer(PinnedReadConsumer):
     def __init__(self, members: List[ReadReq], span_start: int) -> None:
         self.members = members
         self.span_start = span_start
-        self._pinned_block = None
-        self._pinned_nbytes = 0
-        # (expected psum64 of the whole span, word_base) set by the read
-        # scheduler; verified on-device right after the span's single H2D
-        self.expected_psum = None
-
-    def alloc_pinned_buffer(self, nbytes: int) -> memoryview:
-        self._pinned_block = get_pinned_pool().acquire(max(nbytes, 1))
-        self._pinned_nbytes = nbytes
-        return memoryview(self._pinned_block.tensor.numpy())[:nbytes]
-
-    def close(self) -> None:
-        if self._pinned_block is not None:
-            get_pinned_pool().release(self._pinned_block)
-            self._pinned_block = None
 
     def get_consuming_cost_bytes(self) -> int:
         total = 0
@@ -300,13 +279,12 @@ class BatchedBufferConsumer(BufferConsumer):
         """If every member consumes onto the same CUDA device, the whole
         span goes up in ONE H2D and is sliced on the GPU — per-member H2D
         round trips dominate otherwise (measured 0.43 GB/s vs 11.3 GB/s
-        for 2000 small tensors). Members opt in by implementing
+        for 2000 small tensors). Members opt in through
         device_span_target()/consume_from_device_u8() (plain tensor and
         sharded consumers do)."""
         device = None
         for m in self.members:
-            getter = getattr(m.consumer, "device_span_target", None)
-            target = getter() if getter else None
+            target = m.consumer.device_span_target()
             if target is None:
                 return None
             if device is None:
@@ -317,22 +295,17 @@ class BatchedBufferConsumer(BufferConsumer):
 
     def _scatter_members(self):
         """StagingEngine.scatter members for the whole span, or None when
-        the span takes the H2D + per-member copy path instead. Members opt
-        in with ``scatter_members(base_offset, verified) -> list | None``
-        (targets they already hold as results, so nothing is left to do
-        after the launch); one member answering None, or a target on
-        another device, sends the whole span down the other path."""
+        the span takes the H2D + per-member copy path instead: one member
+        answering None to scatter_members(), or a target on another device,
+        sends the whole span down the other path."""
         verified = self.expected_psum is not None
         if verified and not self._members_tile_span():
             return None
         device = self._device_fast_path_target()
         out = []
         for m in self.members:
-            getter = getattr(m.consumer, "scatter_members", None)
-            sub = (
-                getter(m.byte_range[0] - self.span_start, verified)
-                if getter
-                else None
+            sub = m.consumer.scatter_members(
+                m.byte_range[0] - self.span_start, verified
             )
             if sub is None or any(t.device != device for t, _, _ in sub):
                 return None
@@ -353,8 +326,7 @@ class BatchedBufferConsumer(BufferConsumer):
         return True
 
     def will_verify_on_device(self) -> bool:
-        from .ops.staging import HIP_EXT_AVAILABLE
-
+        # with or without a pinned block: the whole span goes to the device
         return HIP_EXT_AVAILABLE and self._device_fast_path_target() is not None
 
     async def consume_buffer(self, ctx: StageContext, buf: BufferType) -> None:
@@ -368,45 +340,19 @@ class BatchedBufferConsumer(BufferConsumer):
             return
 
         def work() -> None:
-            what = (
+            # the whole span in ONE scatter launch, or one H2D sliced on
+            # the GPU per member
+            dev_span = payload_to_device(
+                self,
+                buf,
+                device,
+                self._scatter_members() if self._pinned_block is not None else None,
+                self.expected_psum,
                 f"{self.members[0].path} span[{self.span_start}:"
-                f"{self.span_start + memoryview(buf).nbytes}]"
+                f"{self.span_start + memoryview(buf).nbytes}]",
             )
-            if self._pinned_block is not None:
-                members = self._scatter_members()
-                if members is not None:
-                    # the whole span in ONE scatter launch, straight out of
-                    # the pinned block
-                    get_staging_engine(device).scatter(
-                        self._pinned_block,
-                        self._pinned_nbytes,
-                        members,
-                        expected_psum=self.expected_psum,
-                        what=what,
-                    )
-                    return
-                # read landed in pinned memory already: straight SDMA H2D
-                n = self._pinned_nbytes
-                dev_span = self._pinned_block.tensor[:n].to(
-                    device, non_blocking=False
-                )
-            else:
-                mv = memoryview(buf)
-                nbytes = mv.nbytes
-                pool = get_pinned_pool()
-                block = pool.acquire(max(nbytes, 1))
-                try:
-                    src = torch.frombuffer(mv, dtype=torch.uint8)
-                    block.tensor[:nbytes].copy_(src)
-                    dev_span = block.tensor[:nbytes].to(
-                        device, non_blocking=False
-                    )
-                finally:
-                    pool.release(block)
-            if self.expected_psum is not None:
-                from .ops.staging import verify_device_psum
-
-                verify_device_psum(dev_span, self.expected_psum, what)
+            if dev_span is None:
+                return
             for m in self.members:
                 s, e = m.byte_range
                 sub = dev_span[s - self.span_start : e - self.span_start]

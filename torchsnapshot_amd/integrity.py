@@ -54,6 +54,19 @@ def _splitmix64_mult(idx):
     return z | np.uint64(1)
 
 
+def format_psum64(value: int) -> str:
+    """The stored form of a psum64 value: ``psum64:<16 hex digits>``."""
+    return "psum64:" + format(value % (1 << 64), "016x")
+
+
+def parse_psum64(text) -> Optional[int]:
+    """The value of a stored ``psum64:<hex>`` string; None for anything
+    else (an ``xxh3:`` or legacy untagged checksum, a missing entry)."""
+    if isinstance(text, str) and text.startswith("psum64:"):
+        return int(text[len("psum64:"):], 16)
+    return None
+
+
 def psum64_hexdigest(buf, word_base: int = 0) -> str:
     """psum64 of ``buf``. ``word_base`` is the u64 word index of the
     buffer's first byte within the containing file, so subrange checksums
@@ -72,13 +85,11 @@ def psum64_hexdigest(buf, word_base: int = 0) -> str:
         mv = mv.cast("B")
     nbytes = mv.nbytes
     if nbytes == 0:
-        return "psum64:" + format(0, "016x")
+        return format_psum64(0)
     try:
         from . import _csnap
 
-        return "psum64:" + format(
-            _csnap.psum64_host(mv, word_base) % (1 << 64), "016x"
-        )
+        return format_psum64(_csnap.psum64_host(mv, word_base))
     except ImportError:
         pass
     total = 0
@@ -96,7 +107,7 @@ def psum64_hexdigest(buf, word_base: int = 0) -> str:
         total = (total + _psum_torch_chunk(words, idx)) % (1 << 64)
         wb += words.numel()
         off = end
-    return "psum64:" + format(total, "016x")
+    return format_psum64(total)
 
 
 def _psum_torch_chunk(words: "torch.Tensor", idx: "torch.Tensor") -> int:
@@ -192,7 +203,7 @@ def len_key(path: str) -> str:
 
 def psum64_value(buf, word_base: int = 0) -> int:
     """psum64 as an integer (for accumulating partial sums)."""
-    return int(psum64_hexdigest(buf, word_base)[len("psum64:"):], 16)
+    return parse_psum64(psum64_hexdigest(buf, word_base))
 
 
 def expected_span_psum(
@@ -207,14 +218,15 @@ def expected_span_psum(
     total = 0
     found = False
     for k, v in expected.items():
-        if not k.startswith(prefix) or not v.startswith("psum64:"):
+        value = parse_psum64(v) if k.startswith(prefix) else None
+        if value is None:
             continue
         s_str, _, e_str = k[len(prefix):].partition("-")
         if not (s_str.isdigit() and e_str.isdigit()):
             continue
         s, e = int(s_str), int(e_str)
         if s >= start and e <= end:
-            total = (total + int(v[len("psum64:"):], 16)) % (1 << 64)
+            total = (total + value) % (1 << 64)
             found = True
     return total if found else None
 
@@ -245,7 +257,7 @@ def verify_ranged_buffer(
         )
         return False
     got = psum64_hexdigest(buf, word_base=start // 8)
-    want = "psum64:" + format(total, "016x")
+    want = format_psum64(total)
     if got != want:
         raise RuntimeError(
             f"checksum mismatch for span '{path}' [{start}:{end}): snapshot "
@@ -259,7 +271,7 @@ def verify_buffer(path: str, buf, expected: Dict[str, str]) -> None:
     want = expected.get(path)
     if want is None:
         return
-    if want.startswith("psum64:"):
+    if parse_psum64(want) is not None:
         got = psum64_hexdigest(buf)
     else:
         got = hash_buffer(buf)

@@ -20,7 +20,6 @@ import torch
 
 from .. import knobs
 from ..io_types import (
-    BufferConsumer,
     BufferType,
     ReadReq,
     StageContext,
@@ -28,6 +27,7 @@ from ..io_types import (
 )
 from ..manifest import Shard as ShardMeta
 from ..manifest import ShardedTensorEntry, TensorEntry
+from ..ops.staging import HIP_EXT_AVAILABLE, scatter_member
 from ..serialization import (
     SERIALIZER_BUFFER,
     dtype_to_str,
@@ -35,6 +35,7 @@ from ..serialization import (
     tensor_from_memoryview,
     torch_load_from_bytes,
 )
+from .pinned_read import PinnedReadConsumer, payload_to_device, view_payload
 from .tensor import LoadFuture, TensorIOPreparer, tensor_copy
 
 logger = logging.getLogger(__name__)
@@ -134,7 +135,7 @@ def location_for_shard(storage_path: str, offsets: Sequence[int]) -> str:
 # ---------------------------------------------------------------------------
 
 
-class ShardConsumer(BufferConsumer):
+class ShardConsumer(PinnedReadConsumer):
     """Deserialize one persisted shard and scatter it into every
     overlapping target view."""
 
@@ -145,30 +146,11 @@ class ShardConsumer(BufferConsumer):
     ) -> None:
         self.shard_entry = shard_entry
         self.targets = targets
-        self._pinned_block = None
-        self._pinned_nbytes = 0
-        # (expected psum64 value, word_base) set by the read scheduler
-        # when this consumer verifies on device (will_verify_on_device)
-        self.expected_psum = None
 
     def all_targets_on_device(self) -> bool:
         return bool(self.targets) and all(
             dst.device.type == "cuda" for dst, _ in self.targets
         )
-
-    def alloc_pinned_buffer(self, nbytes: int) -> memoryview:
-        from ..ops.staging import get_pinned_pool
-
-        self._pinned_block = get_pinned_pool().acquire(max(nbytes, 1))
-        self._pinned_nbytes = nbytes
-        return memoryview(self._pinned_block.tensor.numpy())[:nbytes]
-
-    def close(self) -> None:
-        if self._pinned_block is not None:
-            from ..ops.staging import get_pinned_pool
-
-            get_pinned_pool().release(self._pinned_block)
-            self._pinned_block = None
 
     def get_consuming_cost_bytes(self) -> int:
         return self.shard_entry.nbytes_estimate()
@@ -182,25 +164,18 @@ class ShardConsumer(BufferConsumer):
         return None
 
     def will_verify_on_device(self) -> bool:
-        from ..ops.staging import HIP_EXT_AVAILABLE
-
+        # only the pinned -> device path checksums on the GPU
         return (
             HIP_EXT_AVAILABLE
             and self._pinned_block is not None
-            and self.all_targets_on_device()
-            and self.shard_entry.serializer != "torch_save"
+            and self.device_span_target() is not None
         )
 
     def scatter_members(self, base_offset: int, verified: bool = False):
-        """StagingEngine.scatter members that restore this shard from a
-        pinned read whose byte ``base_offset`` is the shard's first, or
-        None when it needs the torch path: every overlap's source box has
-        to be a contiguous run of the stored shard, every target eligible
-        and on one device. A ``verified`` (checksummed) scatter hashes only
-        what it scatters, so the members must then cover the shard's bytes
-        exactly once."""
-        from ..ops.staging import scatter_member
-
+        """Every overlap's source box has to be a contiguous run of the
+        stored shard, every target eligible and on one device. A
+        ``verified`` (checksummed) scatter hashes only what it scatters, so
+        the members must then cover the shard's bytes exactly once."""
         if self.shard_entry.serializer != SERIALIZER_BUFFER or not self.targets:
             return None
         stored = str_to_dtype(self.shard_entry.dtype)
@@ -228,12 +203,13 @@ class ShardConsumer(BufferConsumer):
         return members
 
     def consume_from_device_u8(self, dev_u8: torch.Tensor) -> None:
-        dtype = str_to_dtype(self.shard_entry.dtype)
-        shard = (
-            dev_u8.view(dtype).reshape(tuple(self.shard_entry.shape))
-            if dtype != torch.uint8
-            else dev_u8.reshape(tuple(self.shard_entry.shape))
+        self._copy_overlaps(
+            view_payload(
+                dev_u8, str_to_dtype(self.shard_entry.dtype), self.shard_entry.shape
+            )
         )
+
+    def _copy_overlaps(self, shard: torch.Tensor) -> None:
         for dst_view, ov in self.targets:
             src = narrow_nd(shard, ov.src_offsets, ov.lengths)
             dst = narrow_nd(dst_view, ov.dst_offsets, ov.lengths)
@@ -243,61 +219,28 @@ class ShardConsumer(BufferConsumer):
         def work() -> None:
             if self.shard_entry.serializer == "torch_save":
                 shard = torch_load_from_bytes(bytes(buf))
-            elif self._pinned_block is not None and self.all_targets_on_device():
-                n = self._pinned_nbytes
-                members = self.scatter_members(
-                    0, verified=self.expected_psum is not None
-                )
-                if members is not None:
-                    # every overlap in one scatter launch, straight out of
-                    # the pinned block
-                    from ..ops.staging import get_staging_engine
-
-                    get_staging_engine(self.targets[0][0].device).scatter(
-                        self._pinned_block,
-                        n,
-                        members,
-                        expected_psum=self.expected_psum,
-                        what=self.shard_entry.location,
-                    )
-                    return
-                # storage read landed in pinned memory: straight SDMA H2D,
-                # overlap scatter runs on the GPU
-                dtype = str_to_dtype(self.shard_entry.dtype)
-                dev_u8 = self._pinned_block.tensor[:n].to(
-                    self.targets[0][0].device, non_blocking=False
-                )
-                if self.expected_psum is not None:
-                    from ..ops.staging import verify_device_psum
-
-                    verify_device_psum(
-                        dev_u8, self.expected_psum, self.shard_entry.location
-                    )
-                shard = (
-                    dev_u8.view(dtype).reshape(tuple(self.shard_entry.shape))
-                    if dtype != torch.uint8
-                    else dev_u8.reshape(tuple(self.shard_entry.shape))
-                )
             elif self.all_targets_on_device():
-                # byte-range/batched path: pinned bounce + SDMA
-                from ..ops.staging import copy_buffer_via_pinned
-
-                shard = copy_buffer_via_pinned(
+                verified = self.expected_psum is not None
+                dev_u8 = payload_to_device(
+                    self,
                     buf,
-                    dtype=str_to_dtype(self.shard_entry.dtype),
-                    shape=tuple(self.shard_entry.shape),
-                    device=self.targets[0][0].device,
+                    self.targets[0][0].device,
+                    self.scatter_members(0, verified)
+                    if self._pinned_block is not None
+                    else None,
+                    self.expected_psum,
+                    self.shard_entry.location,
                 )
+                if dev_u8 is not None:  # else the scatter kernel did it all
+                    self.consume_from_device_u8(dev_u8)
+                return
             else:
                 shard = tensor_from_memoryview(
                     memoryview(buf),
                     dtype=str_to_dtype(self.shard_entry.dtype),
                     shape=tuple(self.shard_entry.shape),
                 )
-            for dst_view, ov in self.targets:
-                src = narrow_nd(shard, ov.src_offsets, ov.lengths)
-                dst = narrow_nd(dst_view, ov.dst_offsets, ov.lengths)
-                tensor_copy(dst, src)
+            self._copy_overlaps(shard)
 
         await asyncio.get_running_loop().run_in_executor(ctx.executor, work)
 

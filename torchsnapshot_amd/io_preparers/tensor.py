@@ -19,14 +19,15 @@ from typing import Any, List, Optional, Tuple
 import torch
 
 from ..io_types import (
-    BufferConsumer,
     BufferStager,
     BufferType,
     ReadReq,
     StageContext,
     WriteReq,
 )
+from .. import integrity
 from ..manifest import TensorEntry
+from ..ops.staging import HIP_EXT_AVAILABLE, get_staging_engine, scatter_member
 from ..serialization import (
     SERIALIZER_BUFFER,
     SERIALIZER_QTENSOR,
@@ -41,6 +42,7 @@ from ..serialization import (
     torch_load_from_bytes,
     torch_save_as_bytes,
 )
+from .pinned_read import PinnedReadConsumer, payload_to_device, view_payload
 
 
 class LoadFuture:
@@ -221,7 +223,7 @@ class _TiledReadState:
         self.lock = __import__("threading").Lock()
 
 
-class _TensorTileConsumer(BufferConsumer):
+class _TensorTileConsumer(PinnedReadConsumer):
     def __init__(
         self,
         dst_flat_u8: torch.Tensor,
@@ -233,20 +235,6 @@ class _TensorTileConsumer(BufferConsumer):
         self.start = start
         self.end = end
         self.state = state
-        self._pinned_block = None
-
-    def alloc_pinned_buffer(self, nbytes: int) -> memoryview:
-        from ..ops.staging import get_pinned_pool
-
-        self._pinned_block = get_pinned_pool().acquire(max(nbytes, 1))
-        return memoryview(self._pinned_block.tensor.numpy())[:nbytes]
-
-    def close(self) -> None:
-        if self._pinned_block is not None:
-            from ..ops.staging import get_pinned_pool
-
-            get_pinned_pool().release(self._pinned_block)
-            self._pinned_block = None
 
     def get_consuming_cost_bytes(self) -> int:
         return self.end - self.start
@@ -284,8 +272,6 @@ class TensorBufferStager(BufferStager):
         # with torch in _stage_cpu
         self.save_dtype = save_dtype
         self._staged_batch = None  # StagedBatch for device tensors
-        # device staging computes this for free when TSAMD_CHECKSUM=1
-        self.precomputed_checksum = None
 
     def stored_nbytes(self) -> int:
         """Payload bytes as written (after the save_dtype cast, if any)."""
@@ -310,7 +296,6 @@ class TensorBufferStager(BufferStager):
         return await loop.run_in_executor(ctx.executor, self._stage_cpu, ctx)
 
     def _stage_device(self) -> BufferType:
-        from ..ops.staging import get_staging_engine
         from ..uvm_tensor import is_uvm_tensor, uvm_to_cpu
 
         t = self.tensor.detach()
@@ -332,8 +317,6 @@ class TensorBufferStager(BufferStager):
             if self.is_async_snapshot:
                 cpu = cpu.clone()
             return tensor_as_memoryview(cpu.contiguous())
-        from .. import integrity
-
         engine = get_staging_engine(t.device)
         ck = integrity.checksumming_enabled()
         batch = engine.stage(
@@ -343,9 +326,7 @@ class TensorBufferStager(BufferStager):
         )
         batch.wait()  # blocks in executor thread; GIL released inside HIP
         if ck and batch.checksums is not None:
-            self.precomputed_checksum = "psum64:" + format(
-                batch.checksums[0], "016x"
-            )
+            self.precomputed_checksum = integrity.format_psum64(batch.checksums[0])
         self._staged_batch = batch
         return batch.memoryview_of(0)
 
@@ -387,7 +368,7 @@ class TensorBufferStager(BufferStager):
         self.tensor = None  # type: ignore[assignment]
 
 
-class TensorBufferConsumer(BufferConsumer):
+class TensorBufferConsumer(PinnedReadConsumer):
     def __init__(
         self,
         entry: TensorEntry,
@@ -397,27 +378,6 @@ class TensorBufferConsumer(BufferConsumer):
         self.entry = entry
         self.tensor_out = tensor_out
         self.fut = fut
-        self._pinned_block = None
-        self._pinned_nbytes = 0
-        # (expected psum64 value, word_base) set by the read scheduler
-        # when this consumer verifies on device (will_verify_on_device)
-        self.expected_psum = None
-
-    def alloc_pinned_buffer(self, nbytes: int) -> memoryview:
-        """ReadReq.buf_alloc hook: the storage layer reads directly into
-        pinned memory, so H2D needs no bounce copy."""
-        from ..ops.staging import get_pinned_pool
-
-        self._pinned_block = get_pinned_pool().acquire(max(nbytes, 1))
-        self._pinned_nbytes = nbytes
-        return memoryview(self._pinned_block.tensor.numpy())[:nbytes]
-
-    def close(self) -> None:
-        if self._pinned_block is not None:
-            from ..ops.staging import get_pinned_pool
-
-            get_pinned_pool().release(self._pinned_block)
-            self._pinned_block = None
 
     def get_consuming_cost_bytes(self) -> int:
         nbytes = self.entry.nbytes_estimate()
@@ -426,8 +386,6 @@ class TensorBufferConsumer(BufferConsumer):
         return nbytes
 
     def device_span_target(self):
-        # non-None when this consumer can take its bytes as a slice of a
-        # device-resident uint8 span (batched-span restore fast path)
         if (
             self.tensor_out is not None
             and self.tensor_out.device.type == "cuda"
@@ -437,27 +395,16 @@ class TensorBufferConsumer(BufferConsumer):
         return None
 
     def will_verify_on_device(self) -> bool:
-        """True when consume_buffer will take the pinned->H2D device path
-        and can therefore checksum the bytes on-device at HBM speed
-        instead of CPU-hashing them in the read pipeline."""
-        from ..ops.staging import HIP_EXT_AVAILABLE
-
+        # only the pinned -> device path checksums on the GPU
         return (
             HIP_EXT_AVAILABLE
             and self._pinned_block is not None
-            and self.tensor_out is not None
-            and self.tensor_out.device.type == "cuda"
-            and self.entry.serializer == SERIALIZER_BUFFER
+            and self.device_span_target() is not None
         )
 
     def scatter_members(self, base_offset: int, verified: bool = False):
-        """Batched-span member protocol: the StagingEngine.scatter members
-        that restore this consumer from a pinned read whose byte
-        ``base_offset`` is the payload's first, or None when it needs the
-        torch path. The one member covers the payload exactly once, which
-        is what a ``verified`` (checksummed) scatter asks for."""
-        from ..ops.staging import scatter_member
-
+        """The one member covers the payload exactly once, which is what a
+        ``verified`` scatter asks for."""
         out = self.tensor_out
         if (
             out is None
@@ -472,83 +419,43 @@ class TensorBufferConsumer(BufferConsumer):
         return None if member is None else [member]
 
     def consume_from_device_u8(self, dev_u8: torch.Tensor) -> None:
-        dtype = str_to_dtype(self.entry.dtype)
-        loaded = (
-            dev_u8.view(dtype).reshape(tuple(self.entry.shape))
-            if dtype != torch.uint8
-            else dev_u8.reshape(tuple(self.entry.shape))
+        loaded = view_payload(
+            dev_u8, str_to_dtype(self.entry.dtype), self.entry.shape
         )
         tensor_copy(self.tensor_out, loaded)
         self.fut.obj = self.tensor_out
 
     async def consume_buffer(self, ctx: StageContext, buf: BufferType) -> None:
         def work() -> None:
-            dtype = (
-                str_to_dtype(self.entry.dtype)
-                if self.entry.serializer == SERIALIZER_BUFFER
-                else None
-            )
+            out = self.tensor_out
             if self.entry.serializer == SERIALIZER_QTENSOR:
                 loaded = qtensor_from_bytes(buf)
             elif self.entry.serializer == SERIALIZER_TORCH_SAVE:
                 loaded = torch_load_from_bytes(bytes(buf))
-            elif (
-                self._pinned_block is not None
-                and self.tensor_out is not None
-                and self.tensor_out.device.type == "cuda"
-            ):
-                n = self._pinned_nbytes
-                members = self.scatter_members(0)
-                if members is not None:
-                    # one scatter launch straight out of the pinned block:
-                    # no device-side copy of the payload, widening and the
-                    # checksum fused in
-                    from ..ops.staging import get_staging_engine
-
-                    get_staging_engine(self.tensor_out.device).scatter(
-                        self._pinned_block,
-                        n,
-                        members,
-                        expected_psum=self.expected_psum,
-                        what=self.entry.location,
-                    )
-                    self.fut.obj = self.tensor_out
-                    return
-                # buffer already lives in pinned memory: straight SDMA H2D
-                dev_u8 = self._pinned_block.tensor[:n].to(
-                    self.tensor_out.device, non_blocking=False
-                )
-                if self.expected_psum is not None:
-                    from ..ops.staging import verify_device_psum
-
-                    verify_device_psum(
-                        dev_u8, self.expected_psum, self.entry.location
-                    )
-                loaded = (
-                    dev_u8.view(dtype).reshape(tuple(self.entry.shape))
-                    if dtype != torch.uint8
-                    else dev_u8.reshape(tuple(self.entry.shape))
-                )
-            elif (
-                self.tensor_out is not None
-                and self.tensor_out.device.type == "cuda"
-            ):
-                # batched-span slice: pinned bounce + SDMA H2D
-                from ..ops.staging import copy_buffer_via_pinned
-
-                loaded = copy_buffer_via_pinned(
+            elif out is not None and out.device.type == "cuda":
+                dev_u8 = payload_to_device(
+                    self,
                     buf,
-                    dtype=dtype,
-                    shape=tuple(self.entry.shape),
-                    device=self.tensor_out.device,
+                    out.device,
+                    self.scatter_members(0)
+                    if self._pinned_block is not None
+                    else None,
+                    self.expected_psum,
+                    self.entry.location,
                 )
+                if dev_u8 is None:  # the scatter kernel wrote the target
+                    self.fut.obj = out
+                    return
+                return self.consume_from_device_u8(dev_u8)
             else:
                 loaded = tensor_from_memoryview(
-                    memoryview(buf), dtype=dtype, shape=tuple(self.entry.shape)
+                    memoryview(buf),
+                    dtype=str_to_dtype(self.entry.dtype),
+                    shape=tuple(self.entry.shape),
                 )
-            if self.tensor_out is not None:
-                tensor_copy(self.tensor_out, loaded)
-                self.fut.obj = self.tensor_out
+            if out is not None:
+                tensor_copy(out, loaded)
+                self.fut.obj = out
             else:
                 self.fut.obj = loaded
 

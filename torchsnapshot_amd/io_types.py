@@ -32,6 +32,13 @@ class StageContext:
 
 
 class BufferStager(abc.ABC):
+    # "psum64:<hex>" of the staged bytes when staging computed it anyway
+    # (the gather kernel does); the write pipeline then skips its own hash
+    precomputed_checksum: Optional[str] = None
+    # [(start, end, "psum64:<hex>")] per slab member, so byte-range and
+    # merged-span reads of the slab can be verified on restore
+    member_checksums: Optional[list] = None
+
     @abc.abstractmethod
     async def stage_buffer(self, ctx: StageContext) -> BufferType:
         """Produce the serialized bytes for this write request."""
@@ -45,6 +52,15 @@ class BufferStager(abc.ABC):
 
 
 class BufferConsumer(abc.ABC):
+    """Only the two abstract methods are required. The rest is the protocol
+    the read scheduler and the span batcher speak to device-bound consumers;
+    the defaults describe a consumer that takes host bytes and nothing else."""
+
+    # (psum64 value, word_base) the read scheduler sets before consume_buffer
+    # when will_verify_on_device() answered True: the consumer must then
+    # check the payload on the device and raise on a mismatch
+    expected_psum: Optional[Tuple[int, int]] = None
+
     @abc.abstractmethod
     async def consume_buffer(self, ctx: StageContext, buf: BufferType) -> None:
         """Apply the read bytes to the destination object."""
@@ -56,6 +72,31 @@ class BufferConsumer(abc.ABC):
     def close(self) -> None:
         """Called when the pipeline is done with this request (success or
         failure); return pooled buffers here."""
+
+    def will_verify_on_device(self) -> bool:
+        """Asked after the read landed: True when consume_buffer will take
+        the bytes to the GPU and can checksum them there, so the scheduler
+        hands over ``expected_psum`` instead of hashing on the CPU."""
+        return False
+
+    def device_span_target(self) -> Optional[Any]:
+        """The device on which this consumer can take its bytes as a slice
+        of a device-resident uint8 span (consume_from_device_u8), or None."""
+        return None
+
+    def scatter_members(
+        self, base_offset: int, verified: bool = False
+    ) -> Optional[list]:
+        """StagingEngine.scatter members that complete this consumer from a
+        pinned read whose byte ``base_offset`` is the payload's first, or
+        None when it needs another path. For a ``verified`` (checksummed)
+        scatter they must cover the payload exactly once."""
+        return None
+
+    def consume_from_device_u8(self, dev_u8: Any) -> None:
+        """Apply the payload given as a contiguous device uint8 tensor.
+        Required of consumers whose device_span_target() is not None."""
+        raise NotImplementedError
 
 
 @dataclass

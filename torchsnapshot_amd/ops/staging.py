@@ -607,12 +607,13 @@ class PinnedPool:
         self._allocated = 0
         self._cond = threading.Condition()
 
+    def _alloc(self, nbytes: int) -> torch.Tensor:
+        """Every block's memory comes from here."""
+        return torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+
     def acquire(self, nbytes: int) -> PinnedBlock:
         if nbytes > self.block_size:
-            return PinnedBlock(
-                torch.empty(nbytes, dtype=torch.uint8, pin_memory=True),
-                pooled=False,
-            )
+            return PinnedBlock(self._alloc(nbytes), pooled=False)
         with self._cond:
             while True:
                 if self._free:
@@ -621,10 +622,7 @@ class PinnedPool:
                     self._allocated += 1
                     break
                 self._cond.wait()
-        return PinnedBlock(
-            torch.empty(self.block_size, dtype=torch.uint8, pin_memory=True),
-            pooled=True,
-        )
+        return PinnedBlock(self._alloc(self.block_size), pooled=True)
 
     def release(self, block: PinnedBlock) -> None:
         if not block.pooled:
@@ -641,7 +639,7 @@ class PinnedPool:
             if self._allocated >= self.max_blocks:
                 return False
             self._allocated += 1
-        tensor = torch.empty(self.block_size, dtype=torch.uint8, pin_memory=True)
+        tensor = self._alloc(self.block_size)
         with self._cond:
             self._free.append(tensor)
             self._cond.notify()
@@ -1080,29 +1078,6 @@ def _pack_mode() -> str:
     if mode not in ("slab", "direct"):
         raise ValueError(f"TSAMD_STAGE_MODE must be slab|direct, got {mode}")
     return mode
-
-
-def copy_buffer_via_pinned(
-    buf, dtype: torch.dtype, shape: Sequence[int], device: torch.device
-) -> torch.Tensor:
-    """Restore fast path: host buffer -> pinned bounce -> SDMA H2D.
-
-    Returns a contiguous device tensor with the buffer's content. The
-    pageable-copy alternative (torch.frombuffer(...).to(cuda)) measures
-    ~3x slower on MI355X."""
-    mv = memoryview(buf)
-    nbytes = mv.nbytes
-    pool = get_pinned_pool()
-    block = pool.acquire(max(nbytes, 1))
-    try:
-        src = torch.frombuffer(mv, dtype=torch.uint8)
-        block.tensor[:nbytes].copy_(src)  # releases the GIL
-        dev_u8 = block.tensor[:nbytes].to(device, non_blocking=False)
-    finally:
-        pool.release(block)
-    if dtype == torch.uint8:
-        return dev_u8.reshape(tuple(shape))
-    return dev_u8.view(dtype).reshape(tuple(shape))
 
 
 def device_psum64(dev_u8: torch.Tensor, file_byte_off: int = 0) -> int:

@@ -257,9 +257,8 @@ def execute_write_reqs(
                     stats.stage_s += time.monotonic() - t0
                 nbytes = memoryview(buf).nbytes
                 if do_checksum:
-                    pre = getattr(req.stager, "precomputed_checksum", None)
-                    if pre is not None:
-                        checksums[req.path] = pre
+                    if req.stager.precomputed_checksum is not None:
+                        checksums[req.path] = req.stager.precomputed_checksum
                     else:
                         # psum64 for host-staged payloads too (native
                         # single-pass hash, ~14 GB/s): every file shares
@@ -271,9 +270,7 @@ def execute_write_reqs(
                         )
                     # per-member values so byte-range/merged-span reads of
                     # batched slabs are verifiable on restore
-                    for s, e, v in (
-                        getattr(req.stager, "member_checksums", None) or []
-                    ):
+                    for s, e, v in req.stager.member_checksums or []:
                         checksums[integrity.member_key(req.path, s, e)] = v
                     # file length, so TILED byte-range reads of this file
                     # can be verified once their union covers the file
@@ -411,21 +408,18 @@ def execute_read_reqs(
                     # right after their H2D copy (HBM-speed hash; a CPU
                     # hash here would bottleneck a warm 50 GB/s restore)
                     dev_exp = None
-                    try:
-                        if req.consumer.will_verify_on_device():
-                            if req.byte_range is None:
-                                want = checksums.get(req.path, "")
-                                if want.startswith("psum64:"):
-                                    dev_exp = (int(want[7:], 16), 0)
-                            else:
-                                s0, e0 = req.byte_range
-                                total = integrity.expected_span_psum(
-                                    req.path, req.byte_range, checksums
-                                )
-                                if total is not None and s0 % 8 == 0:
-                                    dev_exp = (total, s0 // 8)
-                    except AttributeError:
-                        pass
+                    if req.consumer.will_verify_on_device():
+                        if req.byte_range is None:
+                            total = integrity.parse_psum64(checksums.get(req.path))
+                            if total is not None:
+                                dev_exp = (total, 0)
+                        else:
+                            s0 = req.byte_range[0]
+                            total = integrity.expected_span_psum(
+                                req.path, req.byte_range, checksums
+                            )
+                            if total is not None and s0 % 8 == 0:
+                                dev_exp = (total, s0 // 8)
                     if dev_exp is not None:
                         req.consumer.expected_psum = dev_exp
                     elif req.byte_range is None:
@@ -439,12 +433,8 @@ def execute_read_reqs(
                             req.path, buf, req.byte_range, checksums,
                         )
                         s, e = req.byte_range
-                        whole = checksums.get(req.path, "")
-                        if (
-                            not verified
-                            and whole.startswith("psum64:")
-                            and s % 8 == 0
-                        ):
+                        whole = integrity.parse_psum64(checksums.get(req.path))
+                        if not verified and whole is not None and s % 8 == 0:
                             # tiled read of an unbatched file: accumulate
                             # the partial sum; once the tiles cover the
                             # whole file, the total is checked below
@@ -488,7 +478,7 @@ def execute_read_reqs(
                     covered = e
                 if covered != int(want_len):
                     continue  # partial coverage: cannot verify
-                got = "psum64:" + format(total, "016x")
+                got = integrity.format_psum64(total)
                 if got != want:
                     raise RuntimeError(
                         f"checksum mismatch for tiled read of '{path}': "
