@@ -16,8 +16,11 @@ dtensor.py:63-278.
 
 from __future__ import annotations
 
+import contextlib
+import copy
 import logging
-from typing import Any, List, Optional, Tuple
+import threading
+from typing import Any, Dict, Iterator, List, Optional, Tuple
 
 import torch
 
@@ -33,6 +36,66 @@ from .sharded_tensor import (
 from .tensor import LoadFuture, TensorIOPreparer
 
 logger = logging.getLogger(__name__)
+
+
+class _PlanMemo:
+    """What the DTensors of one take share. A model's parameters sit on one
+    or two meshes with a handful of distinct (placements, shape) pairs, and
+    ``DeviceMesh.mesh`` alone rebuilds a tensor on every access. Keys use
+    the mesh object's identity; the object is held in the value, so an id
+    cannot be reused while the memo lives."""
+
+    def __init__(self) -> None:
+        # id(device_mesh) -> (device_mesh, mesh tensor, mesh as nested list)
+        self.meshes: Dict[int, Tuple[Any, torch.Tensor, list]] = {}
+        # (id(device_mesh), placements) -> sorted replica set
+        self.replica_sets: Dict[Any, List[int]] = {}
+        # (id(device_mesh), placements, shape) ->
+        #     (local shape, global offset, dim map)
+        self.layouts: Dict[Any, Tuple[List[int], List[int], List[List[int]]]] = {}
+
+
+_plan_state = threading.local()
+
+
+@contextlib.contextmanager
+def planning_memo() -> Iterator[None]:
+    """Scope of one take's planning loop: inside it, prepare_write computes
+    what depends only on the mesh once per mesh, and what depends only on
+    (mesh, placements, global shape) once per distinct triple. The entries
+    it returns are the ones it returns outside the scope."""
+    prev = getattr(_plan_state, "memo", None)
+    _plan_state.memo = prev if prev is not None else _PlanMemo()
+    try:
+        yield
+    finally:
+        _plan_state.memo = prev
+
+
+def _memo_mesh(memo: _PlanMemo, device_mesh: Any) -> Tuple[Any, torch.Tensor, list]:
+    hit = memo.meshes.get(id(device_mesh))
+    if hit is None:
+        mesh = device_mesh.mesh
+        hit = memo.meshes[id(device_mesh)] = (device_mesh, mesh, mesh.tolist())
+    return hit
+
+
+def _mesh_tensor(dt: Any) -> torch.Tensor:
+    """The mesh tensor of the DTensor's device mesh."""
+    memo = getattr(_plan_state, "memo", None)
+    if memo is None:
+        return dt.device_mesh.mesh
+    return _memo_mesh(memo, dt.device_mesh)[1]
+
+
+def _mesh_list(dt: Any) -> list:
+    """The mesh as a nested list, as a manifest entry stores it."""
+    memo = getattr(_plan_state, "memo", None)
+    if memo is None:
+        return dt.device_mesh.mesh.tolist()
+    # a list of its own per entry: the manifest writer must not see one
+    # object shared between entries
+    return copy.deepcopy(_memo_mesh(memo, dt.device_mesh)[2])
 
 
 def _dim_map(dt: Any) -> List[List[int]]:
@@ -57,37 +120,42 @@ def _local_global_offset(dt: Any) -> Tuple[List[int], List[int]]:
     return list(local_shape), list(global_offset)
 
 
-_replica_set_cache: dict = {}
+def _layout_of(dt: Any) -> Tuple[List[int], List[int], List[List[int]]]:
+    """(local shape, global offset, dim map): functions of the mesh, the
+    placements and the global shape alone."""
+    memo = getattr(_plan_state, "memo", None)
+    if memo is None:
+        return (*_local_global_offset(dt), _dim_map(dt))
+    key = (id(dt.device_mesh), tuple(dt.placements), tuple(dt.shape))
+    hit = memo.layouts.get(key)
+    if hit is None:
+        _memo_mesh(memo, dt.device_mesh)  # holds the mesh object: see _PlanMemo
+        hit = memo.layouts[key] = (*_local_global_offset(dt), _dim_map(dt))
+    return list(hit[0]), list(hit[1]), [list(d) for d in hit[2]]
 
 
 def _my_replica_set(dt: Any) -> List[int]:
     """Global ranks that hold a shard identical to this rank's (the ranks
     reached by varying only replicated mesh dims at this rank's mesh
-    coordinate). Cached per (mesh, placements): a model checkpoint calls
-    this once per parameter with identical inputs, and the mesh tensor
-    math is measurable in the async-stall window under CPU contention."""
-    from torch.distributed.tensor.placement_types import Shard
-
-    mesh = dt.device_mesh.mesh
-    cache_key = (
-        tuple(mesh.flatten().tolist()),
-        tuple(mesh.shape),
-        tuple(str(p) for p in dt.placements),
-        torch.distributed.get_rank() if torch.distributed.is_initialized() else 0,
-    )
-    hit = _replica_set_cache.get(cache_key)
-    if hit is not None:
-        return hit
-    result = _my_replica_set_impl(dt)
-    if len(_replica_set_cache) < 64:
-        _replica_set_cache[cache_key] = result
-    return result
+    coordinate). Inside a take it is computed once per (mesh, placements):
+    a model checkpoint asks once per parameter with identical inputs, and
+    the mesh tensor math is measurable in the async-stall window under CPU
+    contention."""
+    memo = getattr(_plan_state, "memo", None)
+    if memo is None:
+        return _my_replica_set_impl(dt)
+    key = (id(dt.device_mesh), tuple(dt.placements))
+    hit = memo.replica_sets.get(key)
+    if hit is None:
+        _memo_mesh(memo, dt.device_mesh)
+        hit = memo.replica_sets[key] = _my_replica_set_impl(dt)
+    return list(hit)
 
 
 def _my_replica_set_impl(dt: Any) -> List[int]:
     from torch.distributed.tensor.placement_types import Shard
 
-    mesh = dt.device_mesh.mesh
+    mesh = _mesh_tensor(dt)
     sharded_mesh_dims = {
         mesh_dim
         for mesh_dim, p in enumerate(dt.placements)
@@ -118,7 +186,7 @@ class DTensorIOPreparer:
         save_dtype: Optional[torch.dtype] = None,
     ) -> Tuple[DTensorEntry, List[WriteReq]]:
         local = obj.to_local()
-        local_shape, global_offset = _local_global_offset(obj)
+        local_shape, global_offset, dim_map = _layout_of(obj)
         if list(local.shape) != local_shape:
             # padded uneven shard (torch pads the last rank): trim
             local = local[tuple(slice(0, s) for s in local_shape)]
@@ -163,8 +231,8 @@ class DTensorIOPreparer:
             write_reqs.extend(sub_reqs)
         entry = DTensorEntry(
             shards=shards_meta,
-            mesh=obj.device_mesh.mesh.tolist(),
-            dim_map=_dim_map(obj),
+            mesh=_mesh_list(obj),
+            dim_map=dim_map,
             dtype=dtype_to_str(save_dtype or obj.dtype),
             shape=list(obj.shape),
         )

@@ -23,6 +23,7 @@ DEPS = (
     SRC,
     PKG_ROOT / "ops" / "hip" / "desc_check.h",
     PKG_ROOT / "ops" / "hip" / "file_sink.h",
+    PKG_ROOT / "ops" / "hip" / "table_ring.h",
 )
 OUT = PKG_ROOT / f"_csnap{sysconfig.get_config_var('EXT_SUFFIX') or '.so'}"
 

@@ -32,6 +32,9 @@
 //   - on the host (desc_check.h): parse_descs + check_descs validate every
 //     descriptor before the GPU is touched; wu_prefix_of, grid_for and
 //     LaunchTables are the launch prologue of both launchers
+//   - on the host (table_ring.h): the launch tables reach the device
+//     through a ring of pinned slots, so a launch never waits for the
+//     stream it enqueues on, and the launch entry points hold no GIL
 //
 // Design notes (CDNA4):
 //   - wave64; block = 256 threads; work units of 64 KiB of slab bytes,
@@ -55,6 +58,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -64,6 +68,7 @@
 
 #include "desc_check.h"
 #include "file_sink.h"
+#include "table_ring.h"
 
 namespace py = pybind11;
 
@@ -779,21 +784,56 @@ __global__ __launch_bounds__(kBlockThreads) void scan_kernel(
 // host-side op management
 // ---------------------------------------------------------------------------
 
+// The HIP half of a launch-table ring (table_ring.h has the policy): slot
+// i is host + i * slot_bytes, dev + i * slot_bytes and ev[i].
+struct HipTableRing {
+  TableRing policy{kTableRingSlots, kTableRingSlotBytes};
+  char* host = nullptr;  // pinned
+  char* dev = nullptr;
+  hipEvent_t ev[kTableRingSlots] = {};
+
+  void allocate() {
+    const size_t bytes = policy.slots() * policy.slot_bytes();
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&host), bytes,
+                            hipHostMallocDefault));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dev), bytes));
+    for (hipEvent_t& e : ev) {
+      HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+  }
+
+  // whatever allocate() got as far as creating; only for a context whose
+  // set-up failed, a finished one lives as long as the process
+  void release() {
+    for (hipEvent_t& e : ev) {
+      if (e != nullptr) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+    if (dev != nullptr) (void)hipFree(dev);
+    if (host != nullptr) (void)hipHostFree(host);
+    dev = host = nullptr;
+  }
+};
+
+// Lives for the life of the process once created: streams and rings are
+// allocated once per device.
 struct DeviceCtx {
   hipStream_t d2h_stream = nullptr;
   hipStream_t h2d_stream = nullptr;
   hipStream_t verify_stream = nullptr;  // lazily created (psum64_dev)
+  HipTableRing d2h_ring;
+  HipTableRing h2d_ring;
 };
 
 struct Op {
   hipEvent_t ev = nullptr;
   int device = 0;
-  void* scratch = nullptr;  // freed at wait()
-  std::vector<char> host_staging;
 };
 
+// g_mu guards the three maps below and nothing else; the launch entry
+// points run without the GIL, so several threads get here at once
 std::mutex g_mu;
-std::unordered_map<int, DeviceCtx> g_ctx;
+std::unordered_map<int, std::unique_ptr<DeviceCtx>> g_ctx;
 std::unordered_map<long long, Op> g_ops;
 long long g_next_handle = 1;
 
@@ -802,24 +842,35 @@ DeviceCtx& get_ctx(int device) {
   auto it = g_ctx.find(device);
   if (it == g_ctx.end()) {
     HIP_CHECK(hipSetDevice(device));
-    DeviceCtx ctx;
-    HIP_CHECK(hipStreamCreateWithFlags(&ctx.d2h_stream, hipStreamNonBlocking));
-    HIP_CHECK(hipStreamCreateWithFlags(&ctx.h2d_stream, hipStreamNonBlocking));
-    it = g_ctx.emplace(device, ctx).first;
+    auto ctx = std::make_unique<DeviceCtx>();
+    try {
+      HIP_CHECK(
+          hipStreamCreateWithFlags(&ctx->d2h_stream, hipStreamNonBlocking));
+      HIP_CHECK(
+          hipStreamCreateWithFlags(&ctx->h2d_stream, hipStreamNonBlocking));
+      ctx->d2h_ring.allocate();
+      ctx->h2d_ring.allocate();
+    } catch (...) {
+      // nothing of a half-built context stays behind: the next call starts
+      // from scratch
+      ctx->d2h_ring.release();
+      ctx->h2d_ring.release();
+      if (ctx->d2h_stream != nullptr) (void)hipStreamDestroy(ctx->d2h_stream);
+      if (ctx->h2d_stream != nullptr) (void)hipStreamDestroy(ctx->h2d_stream);
+      throw;
+    }
+    it = g_ctx.emplace(device, std::move(ctx)).first;
   }
-  return it->second;
+  return *it->second;
 }
 
-long long register_op(hipEvent_t ev, int device, void* scratch,
-                      std::vector<char>&& staging) {
+long long register_op(hipEvent_t ev, int device) {
   std::lock_guard<std::mutex> lk(g_mu);
   long long h = g_next_handle++;
   Op op;
   op.ev = ev;
   op.device = device;
-  op.scratch = scratch;
-  op.host_staging = std::move(staging);
-  g_ops.emplace(h, std::move(op));
+  g_ops.emplace(h, op);
   return h;
 }
 
@@ -840,14 +891,25 @@ void chain_after(hipStream_t side, uintptr_t producer_stream, int device) {
   }
 }
 
+// The environment is read with the GIL held (os.environ writes hold it
+// too), before an entry point releases it.
+std::string env_or_empty(const char* name) {
+  const char* v = getenv(name);
+  return v ? std::string(v) : std::string();
+}
+
 // One launcher for the three copy entry points. `kind` picks the rules
 // check_descs applies and the kernel family: Gather runs pack_kernel on
 // the D2H side stream, Scatter and Unpack run unpack_kernel on the H2D
-// one (Scatter never casts or hashes).
+// one (Scatter never casts or hashes). Called without the GIL, from any
+// number of threads: nothing here waits for work queued on the stream,
+// except for a ring slot that is still in use sixteen launches later and
+// for a table too large for a slot.
 long long launch_pack(const std::vector<unsigned long long>& flat, int n,
                       DescKind kind, uintptr_t slab_ptr, uintptr_t pinned_ptr,
                       unsigned long long total_bytes, uintptr_t producer_stream,
-                      int device, uintptr_t hash_out_ptr = 0,
+                      int device, const std::string& grid_env,
+                      uintptr_t hash_out_ptr = 0,
                       unsigned long long hash_byte0 = 0) {
   // everything is refused here, before the GPU is touched
   const std::vector<Desc> descs = parse_descs(flat, n);
@@ -880,22 +942,6 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
 
   chain_after(stream, producer_stream, device);
 
-  // descriptors + prefix sums in one device allocation, one copy
-  LaunchTables tables(descs, wu_prefix);
-  void* scratch = nullptr;
-  HIP_CHECK(hipMallocAsync(&scratch, tables.host.size(), stream));
-  HIP_CHECK(hipMemcpyAsync(scratch, tables.host.data(), tables.host.size(),
-                           hipMemcpyHostToDevice, stream));
-  const Desc* d_descs = tables.descs(scratch);
-  const unsigned long long* d_prefix = tables.prefix(scratch);
-
-  if (!gather && slab_ptr != 0) {
-    // restore via slab: H2D copy first, then scatter out of the slab
-    HIP_CHECK(hipMemcpyAsync(reinterpret_cast<void*>(slab_ptr),
-                             reinterpret_cast<void*>(pinned_ptr), total_bytes,
-                             hipMemcpyHostToDevice, stream));
-  }
-
   // Grid cap. Direct mode is PCIe-bound: 128 workgroups already sustain
   // the measured ~51 GB/s host-link ceiling (grid sweep, profiles/), so a
   // small grid leaves the CUs to overlapped training compute. Slab mode
@@ -903,29 +949,92 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
   // restore kernel's reads of pinned memory behave the same way: 128-256
   // workgroups reach the link rate, 1024+ lose a few percent.
   const bool direct_mode = (slab_ptr == 0);
-  const unsigned int grid = grid_for(total_wus, direct_mode ? 256ull : 16384ull,
-                                     getenv("TSAMD_PACK_GRID"));
+  const unsigned int grid =
+      grid_for(total_wus, direct_mode ? 256ull : 16384ull,
+               grid_env.empty() ? nullptr : grid_env.c_str());
   unsigned long long* hash_out =
       reinterpret_cast<unsigned long long*>(hash_out_ptr);
   const bool hash = hash_out != nullptr;
-  if (gather) {
-    auto kernel = any_cast ? (hash ? pack_kernel<true, true>
-                                   : pack_kernel<false, true>)
-                           : (hash ? pack_kernel<true, false>
-                                   : pack_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
-                       d_descs, n, d_prefix, total_wus, flat_base, hash_out);
-  } else {
-    auto kernel = any_cast ? (hash ? unpack_kernel<true, true>
-                                   : unpack_kernel<false, true>)
-                           : (hash ? unpack_kernel<true, false>
-                                   : unpack_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
-                       d_descs, n, d_prefix, total_wus,
-                       static_cast<const char*>(flat_base), hash_out,
-                       hash_byte0);
+
+  // descriptors + prefix sums: one host image, one copy
+  const LaunchTables tables(descs, wu_prefix);
+  const size_t table_bytes = tables.host.size();
+
+  // everything that follows the table upload on the stream, up to and
+  // including the kernel that reads the tables at `d_tables`
+  auto enqueue_kernel = [&](const void* d_tables) {
+    const Desc* d_descs = tables.descs(d_tables);
+    const unsigned long long* d_prefix = tables.prefix(d_tables);
+    if (!gather && slab_ptr != 0) {
+      // restore via slab: H2D copy first, then scatter out of the slab
+      HIP_CHECK(hipMemcpyAsync(reinterpret_cast<void*>(slab_ptr),
+                               reinterpret_cast<void*>(pinned_ptr),
+                               total_bytes, hipMemcpyHostToDevice, stream));
+    }
+    if (gather) {
+      auto kernel = any_cast ? (hash ? pack_kernel<true, true>
+                                     : pack_kernel<false, true>)
+                             : (hash ? pack_kernel<true, false>
+                                     : pack_kernel<false, false>);
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
+                         d_descs, n, d_prefix, total_wus, flat_base, hash_out);
+    } else {
+      auto kernel = any_cast ? (hash ? unpack_kernel<true, true>
+                                     : unpack_kernel<false, true>)
+                             : (hash ? unpack_kernel<true, false>
+                                     : unpack_kernel<false, false>);
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
+                         d_descs, n, d_prefix, total_wus,
+                         static_cast<const char*>(flat_base), hash_out,
+                         hash_byte0);
+    }
+    HIP_CHECK(hipGetLastError());
+  };
+
+  HipTableRing& ring = gather ? ctx.d2h_ring : ctx.h2d_ring;
+  const size_t slot_bytes = ring.policy.slot_bytes();
+  const bool ringed = ring.policy.launch(
+      table_bytes,
+      [&](int slot) { HIP_CHECK(hipEventSynchronize(ring.ev[slot])); },
+      [&](int slot) {
+        char* h_tables = ring.host + slot * slot_bytes;
+        char* d_tables = ring.dev + slot * slot_bytes;
+        std::memcpy(h_tables, tables.host.data(), table_bytes);
+        try {
+          // out of pinned memory: enqueued, not waited for
+          HIP_CHECK(hipMemcpyAsync(d_tables, h_tables, table_bytes,
+                                   hipMemcpyHostToDevice, stream));
+          enqueue_kernel(d_tables);
+          HIP_CHECK(hipEventRecord(ring.ev[slot], stream));
+        } catch (...) {
+          // the slot goes back unrecorded: nothing may still read it
+          (void)hipStreamSynchronize(stream);
+          throw;
+        }
+      });
+  if (!ringed) {
+    // A table larger than a slot (a slab of hundreds of members): a device
+    // allocation of its own and a copy out of pageable memory, which waits
+    // for the stream. The synchronise makes that explicit, so the host
+    // image may go out of scope whatever the runtime did with it.
+    void* scratch = nullptr;
+    HIP_CHECK(hipMallocAsync(&scratch, table_bytes, stream));
+    hipError_t err = hipMemcpyAsync(scratch, tables.host.data(), table_bytes,
+                                    hipMemcpyHostToDevice, stream);
+    const hipError_t sync_err = hipStreamSynchronize(stream);
+    if (err == hipSuccess) err = sync_err;
+    if (err == hipSuccess) {
+      try {
+        enqueue_kernel(scratch);
+      } catch (...) {
+        (void)hipFreeAsync(scratch, stream);
+        throw;
+      }
+    }
+    const hipError_t free_err = hipFreeAsync(scratch, stream);
+    if (err == hipSuccess) err = free_err;
+    HIP_CHECK(err);
   }
-  HIP_CHECK(hipGetLastError());
 
   if (gather && slab_ptr != 0) {
     // slab mode: one SDMA copy moves the packed slab to pinned host memory
@@ -933,13 +1042,15 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
                              reinterpret_cast<void*>(slab_ptr), total_bytes,
                              hipMemcpyDeviceToHost, stream));
   }
-  HIP_CHECK(hipFreeAsync(scratch, stream));
 
   hipEvent_t ev;
   HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  HIP_CHECK(hipEventRecord(ev, stream));
-  // the host image must outlive the copy that reads it
-  return register_op(ev, device, nullptr, std::move(tables.host));
+  const hipError_t rec_err = hipEventRecord(ev, stream);
+  if (rec_err != hipSuccess) {
+    (void)hipEventDestroy(ev);
+    HIP_CHECK(rec_err);
+  }
+  return register_op(ev, device);
 }
 }  // namespace
 
@@ -950,6 +1061,7 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
 static long long d2h_copy(uintptr_t src, uintptr_t dst_pinned,
                           unsigned long long nbytes, uintptr_t producer_stream,
                           int device) {
+  py::gil_scoped_release release;
   HIP_CHECK(hipSetDevice(device));
   DeviceCtx& ctx = get_ctx(device);
   chain_after(ctx.d2h_stream, producer_stream, device);
@@ -958,25 +1070,38 @@ static long long d2h_copy(uintptr_t src, uintptr_t dst_pinned,
                            hipMemcpyDeviceToHost, ctx.d2h_stream));
   hipEvent_t ev;
   HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  HIP_CHECK(hipEventRecord(ev, ctx.d2h_stream));
-  return register_op(ev, device, nullptr, {});
+  const hipError_t rec_err = hipEventRecord(ev, ctx.d2h_stream);
+  if (rec_err != hipSuccess) {
+    (void)hipEventDestroy(ev);
+    HIP_CHECK(rec_err);
+  }
+  return register_op(ev, device);
 }
 
+// The three launch entry points: arguments are converted and the
+// environment read with the GIL held, everything else runs without it. A
+// refusal or a HIP error is a C++ exception; the GIL is taken back while
+// it unwinds, before pybind11 turns it into the Python one.
 static long long pack_d2h(const std::vector<unsigned long long>& flat, int n,
                           uintptr_t slab_ptr, uintptr_t pinned_ptr,
                           unsigned long long total_bytes,
                           uintptr_t producer_stream, int device,
                           uintptr_t hash_out_ptr = 0) {
+  const std::string grid_env = env_or_empty("TSAMD_PACK_GRID");
+  py::gil_scoped_release release;
   return launch_pack(flat, n, DescKind::Gather, slab_ptr, pinned_ptr,
-                     total_bytes, producer_stream, device, hash_out_ptr);
+                     total_bytes, producer_stream, device, grid_env,
+                     hash_out_ptr);
 }
 
 static long long scatter_h2d(const std::vector<unsigned long long>& flat, int n,
                              uintptr_t slab_ptr, uintptr_t pinned_ptr,
                              unsigned long long total_bytes,
                              uintptr_t producer_stream, int device) {
+  const std::string grid_env = env_or_empty("TSAMD_PACK_GRID");
+  py::gil_scoped_release release;
   return launch_pack(flat, n, DescKind::Scatter, slab_ptr, pinned_ptr,
-                     total_bytes, producer_stream, device);
+                     total_bytes, producer_stream, device, grid_env);
 }
 
 static long long unpack_h2d(const std::vector<unsigned long long>& flat,
@@ -985,9 +1110,11 @@ static long long unpack_h2d(const std::vector<unsigned long long>& flat,
                             uintptr_t producer_stream, int device,
                             uintptr_t hash_out_ptr = 0,
                             unsigned long long hash_byte0 = 0) {
+  const std::string grid_env = env_or_empty("TSAMD_PACK_GRID");
+  py::gil_scoped_release release;
   return launch_pack(flat, n, DescKind::Unpack, slab_ptr, pinned_ptr,
-                     total_bytes, producer_stream, device, hash_out_ptr,
-                     hash_byte0);
+                     total_bytes, producer_stream, device, grid_env,
+                     hash_out_ptr, hash_byte0);
 }
 
 // ---------------------------------------------------------------------------
@@ -1265,6 +1392,11 @@ static bool op_query(long long handle) {
   return hipEventQuery(it->second.ev) == hipSuccess;
 }
 
+static size_t pending_ops() {
+  std::lock_guard<std::mutex> lk(g_mu);
+  return g_ops.size();
+}
+
 static bool is_managed_ptr(uintptr_t ptr) {
   hipPointerAttribute_t attr;
   hipError_t e =
@@ -1355,6 +1487,15 @@ PYBIND11_MODULE(_csnap, m) {
         py::arg("chunk_bytes") = 256ll * 1024 * 1024, py::arg("reuse") = true);
   m.def("wait", &op_wait, "block until an op completes");
   m.def("query", &op_query, "poll an op");
+  m.def("pending_ops", &pending_ops,
+        "number of launched ops that have not been waited for");
+  m.def("table_ring_slots", []() { return tsamd::kTableRingSlots; },
+        "slots of each launch-table ring (one ring per device and side "
+        "stream)");
+  m.def("table_ring_slot_bytes",
+        []() { return (unsigned long long)tsamd::kTableRingSlotBytes; },
+        "largest launch table (descriptors + prefix sums) that goes through "
+        "a ring slot; a larger one takes the blocking fallback");
   m.def("is_managed_ptr", &is_managed_ptr);
   m.def("device_count", &device_count);
   m.def("managed_alloc", &managed_alloc, "hipMallocManaged");

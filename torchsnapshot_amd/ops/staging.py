@@ -23,10 +23,11 @@ into the torch fallback (debug only).
 
 from __future__ import annotations
 
+import contextlib
 import math
 import threading
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -660,6 +661,8 @@ def get_pinned_pool() -> PinnedPool:
 
 _warm_stop = threading.Event()
 _warm_thread: Optional[threading.Thread] = None
+# [pool, bytes] the warming thread still has to pin (pool_warming_paused)
+_warm_left: list = [None, 0]
 
 
 def _join_warm_thread() -> None:
@@ -678,8 +681,33 @@ def warm_pinned_pool(nbytes: Optional[int] = None, background: bool = True) -> N
     keeps the FIRST checkpoint as fast as the rest (measured 14.4 s ->
     0.35 s first-async-take stall for an 8 GB model). Called automatically
     (in the background) when a StagingEngine is first created."""
+    _start_warming(get_pinned_pool(), nbytes, background)
+
+
+@contextlib.contextmanager
+def pool_warming_paused() -> Iterator[None]:
+    """Hold background pool warming for the duration: the warming thread
+    stops after the block it is pinning, and what it had left to warm is
+    warmed in the background again afterwards. Pinned allocations take a
+    runtime-wide lock; this is for code that must not share it (a latency
+    measurement, a test of one)."""
+    t = _warm_thread
+    paused = t is not None and t.is_alive()
+    if paused:
+        _warm_stop.set()
+        t.join()
+        _warm_stop.clear()
+    try:
+        yield
+    finally:
+        if paused and _warm_left[1] > 0:
+            _start_warming(_warm_left[0], _warm_left[1], background=True)
+
+
+def _start_warming(
+    pool: PinnedPool, nbytes: Optional[int], background: bool
+) -> None:
     global _warm_thread
-    pool = get_pinned_pool()
 
     def work() -> None:
         import os
@@ -694,12 +722,16 @@ def warm_pinned_pool(nbytes: Optional[int] = None, background: bool = True) -> N
                 int(float(os.environ.get("TSAMD_POOL_WARM_BYTES", 8 * 1024**3))),
             )
         allocated = 0
+        _warm_left[:] = [pool, target]
         while (
             not _warm_stop.is_set()
             and allocated < target
             and pool.prealloc_one()
         ):
             allocated += pool.block_size
+            _warm_left[1] = target - allocated
+        if not _warm_stop.is_set():
+            _warm_left[1] = 0  # done, or the pool is full
 
     if background:
         import atexit

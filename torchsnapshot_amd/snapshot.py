@@ -37,6 +37,7 @@ from .dist_store import LinearBarrier, get_or_create_store
 from .event import Event, log_event
 from .flatten import Flattened, flatten, inflate
 from .io_preparer import prepare_read, prepare_write
+from .io_preparers.dtensor import planning_memo
 from .io_types import ReadReq, StoragePlugin, WriteIO, WriteReq
 from .manifest import (
     ChunkedTensorEntry,
@@ -460,45 +461,48 @@ class Snapshot:
         # aliases SHARE the writer's entry object, so batcher relocation
         # stays consistent for every path
         seen_tensors: Dict[Any, Entry] = {}
-        for logical_path, obj in flattened.items():
-            alias_key = None
-            # shadow clones above stay in the source dtype; the narrowing
-            # happens at staging time
-            target_dtype = _resolve_save_dtype(
-                save_dtype_rules, logical_path, obj
-            )
-            if (
-                isinstance(obj, torch.Tensor)
-                and type(obj) is torch.Tensor
-                and not obj.is_quantized
-                and obj.layout == torch.strided  # sparse has no data_ptr
-            ):
-                alias_key = (
-                    obj.data_ptr(),
-                    obj.dtype,
-                    tuple(obj.shape),
-                    tuple(obj.stride()),
-                    str(obj.device),
-                    logical_path in replicated_paths,
-                    target_dtype,
+        # one planning scope per take: the DTensor preparer computes what
+        # the leaves share (mesh, replica set, shard layout) once
+        with planning_memo():
+            for logical_path, obj in flattened.items():
+                alias_key = None
+                # shadow clones above stay in the source dtype; the
+                # narrowing happens at staging time
+                target_dtype = _resolve_save_dtype(
+                    save_dtype_rules, logical_path, obj
                 )
-                if alias_key in seen_tensors:
-                    manifest[logical_path] = seen_tensors[alias_key]
-                    continue
-            entry, reqs = prepare_write(
-                obj=obj,
-                logical_path=logical_path,
-                rank=rank,
-                replicated=logical_path in replicated_paths,
-                is_async_snapshot=is_async,
-                save_dtype=target_dtype,
-            )
-            manifest[logical_path] = entry
-            if alias_key is not None:
-                seen_tensors[alias_key] = entry
-            for r in reqs:
-                req_to_logical[r.path] = logical_path
-            write_reqs.extend(reqs)
+                if (
+                    isinstance(obj, torch.Tensor)
+                    and type(obj) is torch.Tensor
+                    and not obj.is_quantized
+                    and obj.layout == torch.strided  # sparse: no data_ptr
+                ):
+                    alias_key = (
+                        obj.data_ptr(),
+                        obj.dtype,
+                        tuple(obj.shape),
+                        tuple(obj.stride()),
+                        str(obj.device),
+                        logical_path in replicated_paths,
+                        target_dtype,
+                    )
+                    if alias_key in seen_tensors:
+                        manifest[logical_path] = seen_tensors[alias_key]
+                        continue
+                entry, reqs = prepare_write(
+                    obj=obj,
+                    logical_path=logical_path,
+                    rank=rank,
+                    replicated=logical_path in replicated_paths,
+                    is_async_snapshot=is_async,
+                    save_dtype=target_dtype,
+                )
+                manifest[logical_path] = entry
+                if alias_key is not None:
+                    seen_tensors[alias_key] = entry
+                for r in reqs:
+                    req_to_logical[r.path] = logical_path
+                write_reqs.extend(reqs)
 
         # replicated write-load balancing
         if world_size > 1 and not knobs.is_partitioner_disabled():
