@@ -1,7 +1,8 @@
 """CPU mirror of the HIP pack kernel's gather math.
 
-``py_pack`` reproduces, in Python, exactly the address computation the
-pack kernel performs from a PackItem descriptor (row decomposition over
+``py_pack`` (tests/_layout_sweep.py) reproduces, in Python, exactly the
+address computation the pack kernel performs from a PackItem descriptor
+(row decomposition over
 outer dims, innermost contiguous run). Its output must equal
 ``t.contiguous()``'s bytes for every layout — the same oracle the GPU
 numerics tests use (plain torch fp32 reference)."""
@@ -9,44 +10,13 @@ numerics tests use (plain torch fp32 reference)."""
 import pytest
 import torch
 
+from _layout_sweep import py_pack, ref_bytes
+
 from torchsnapshot_amd.ops.staging import (
     ALIGN,
     build_pack_items,
     collapse_layout,
 )
-
-
-def py_pack(t: torch.Tensor) -> bytes:
-    items, _, _ = build_pack_items([t])
-    it = items[0]
-    if it.nbytes == 0:
-        return b""
-    storage = t.untyped_storage()
-    # read the storage bytes directly
-    u8 = torch.empty(storage.nbytes(), dtype=torch.uint8)
-    u8.untyped_storage().copy_(storage)
-    storage_b = bytes(u8.numpy())
-    base = t.data_ptr() - storage.data_ptr()
-    rb = it.row_bytes
-    out = bytearray(it.nbytes)
-    rows = it.nbytes // rb
-    for r in range(rows):
-        off = 0
-        rem = r
-        for k in reversed(range(len(it.outer_sizes))):
-            idx = rem % it.outer_sizes[k]
-            rem //= it.outer_sizes[k]
-            off += idx * it.outer_strides[k]
-        src = base + off
-        out[r * rb : (r + 1) * rb] = storage_b[src : src + rb]
-    return bytes(out)
-
-
-def ref_bytes(t: torch.Tensor) -> bytes:
-    c = t.contiguous().reshape(-1)
-    if c.numel() == 0:
-        return b""
-    return bytes(c.view(torch.uint8).numpy())
 
 
 _CASES = [

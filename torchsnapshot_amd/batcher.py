@@ -37,6 +37,7 @@ from .ops.staging import (
     HIP_EXT_AVAILABLE,
     build_pack_items,
     get_staging_engine,
+    resolve_lazy,
 )
 from .serialization import SERIALIZER_BUFFER, tensor_as_memoryview
 
@@ -174,6 +175,7 @@ class BatchedBufferStager(BufferStager):
         ck = integrity.checksumming_enabled()
         members = []
         for t, off, out_dtype in zip(self.tensors, offsets, self.out_dtypes):
+            t = resolve_lazy(t)  # lazy conj/neg views are saved by value
             if out_dtype is not None and out_dtype != t.dtype:
                 t = t.to(out_dtype)
             nbytes = t.numel() * t.element_size()

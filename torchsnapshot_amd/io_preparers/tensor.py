@@ -27,7 +27,12 @@ from ..io_types import (
 )
 from .. import integrity
 from ..manifest import TensorEntry
-from ..ops.staging import HIP_EXT_AVAILABLE, get_staging_engine, scatter_member
+from ..ops.staging import (
+    HIP_EXT_AVAILABLE,
+    get_staging_engine,
+    resolve_lazy,
+    scatter_member,
+)
 from ..serialization import (
     SERIALIZER_BUFFER,
     SERIALIZER_QTENSOR,
@@ -298,7 +303,8 @@ class TensorBufferStager(BufferStager):
     def _stage_device(self) -> BufferType:
         from ..uvm_tensor import is_uvm_tensor, uvm_to_cpu
 
-        t = self.tensor.detach()
+        # a lazy conj/neg view is saved by value, on every branch below
+        t = resolve_lazy(self.tensor.detach())
         if t.is_quantized or self.serializer != SERIALIZER_BUFFER:
             # rare path: bring to host with torch, then pack
             cpu = t.cpu()
@@ -331,7 +337,10 @@ class TensorBufferStager(BufferStager):
         return batch.memoryview_of(0)
 
     def _stage_cpu(self, ctx: StageContext) -> BufferType:
-        t = self.tensor.detach()
+        # resolved first: tensor_as_memoryview cannot view a lazy conj/neg
+        # tensor's bytes, and they would be the unresolved ones
+        src = self.tensor.detach()
+        t = resolve_lazy(src)
         if self.serializer == SERIALIZER_QTENSOR:
             return qtensor_as_bytes(t)
         if self.serializer == SERIALIZER_TORCH_SAVE:
@@ -340,7 +349,8 @@ class TensorBufferStager(BufferStager):
             # runs on the executor thread; the cast result is a private
             # copy, so async snapshots need no extra clone
             return tensor_as_memoryview(t.to(self.save_dtype).contiguous())
-        if self._should_copy_cpu_tensor(t, ctx):
+        # a resolved lazy view is a private copy already
+        if t is src and self._should_copy_cpu_tensor(t, ctx):
             t = t.contiguous().clone() if not t.is_contiguous() else t.clone()
         elif not t.is_contiguous():
             t = t.contiguous()

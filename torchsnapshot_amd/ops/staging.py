@@ -85,6 +85,31 @@ def collapse_layout(t: torch.Tensor) -> Tuple[List[int], List[int]]:
     return merged_sizes, merged_strides
 
 
+def outer_dim_count(t: torch.Tensor) -> int:
+    """Strided dims left for the kernels to decompose after collapsing: all
+    collapsed dims but an innermost contiguous row."""
+    sizes, strides = collapse_layout(t)
+    return len(sizes) - 1 if strides[-1] == 1 else len(sizes)
+
+
+MAX_OUTER_DIMS = 6  # kMaxDims in ops/hip/desc_check.h
+
+
+def resolve_lazy(t: torch.Tensor) -> torch.Tensor:
+    """``t`` with a lazy conjugate or negative bit applied to its bytes.
+
+    ``x.conj()`` and ``torch._neg_view(x)`` share ``x``'s memory, sizes and
+    strides and differ from it only in a flag, so anything that describes
+    raw memory has to resolve them first or it saves ``x``. ``detach()``
+    and ``contiguous()`` keep the bits. Resolving changes neither numel
+    nor dtype, and a tensor without the bits is returned as it is."""
+    if t.is_conj():
+        t = t.resolve_conj()
+    if t.is_neg():
+        t = t.resolve_neg()
+    return t
+
+
 @dataclass
 class PackItem:
     """One tensor's gather descriptor inside a slab."""
@@ -335,9 +360,7 @@ def _scatter_layout_plan(
         return None
     if torch._debug_has_internal_overlap(target) != 0:
         return None
-    sizes, strides = collapse_layout(target)
-    n_outer = len(sizes) - 1 if strides[-1] == 1 else len(sizes)
-    if n_outer > 6:
+    if outer_dim_count(target) > MAX_OUTER_DIMS:
         return None
     if target.numel() * stored_dtype.itemsize >= _KERNEL_MAX_BYTES:
         return None
@@ -836,10 +859,14 @@ class StagingEngine:
         The caller must ensure the tensors' producing stream is
         torch.cuda.current_stream() of this thread (true for checkpointing:
         tensors are live parameters/opt states, already materialized)."""
-        # the pack kernel indexes within-tensor bytes as u32: materialize
-        # non-contiguous tensors over 2 GiB first (chunking splits along
-        # dim 0 upstream, so this is rare). The stride>=0 check is
-        # defensive only — torch itself forbids negative strides.
+        # descriptors state raw memory: a lazily conjugated or negated
+        # tensor is saved by value. The pack kernel indexes within-tensor
+        # bytes as u32 and decomposes at most 6 outer dims: materialize
+        # non-contiguous tensors over 2 GiB or beyond 6 dims first
+        # (chunking splits along dim 0 upstream, and such layouts are
+        # rare). The stride>=0 check is defensive only — torch itself
+        # forbids negative strides.
+        tensors = [resolve_lazy(t) for t in tensors]
         tensors = [
             t
             if (
@@ -847,6 +874,7 @@ class StagingEngine:
                 or (
                     t.numel() * t.element_size() < 2**31
                     and all(s >= 0 for s in t.stride())
+                    and outer_dim_count(t) <= MAX_OUTER_DIMS
                 )
             )
             else t.contiguous()
