@@ -9,6 +9,7 @@ backend on ROCm) or gloo.
 """
 
 from .nonfinite import NonFiniteStateError, find_nonfinite
+from .replication import ReplicatedStateMismatchError, fingerprint_state
 from .rng_state import RNGState
 from .snapshot import PendingSnapshot, Snapshot
 from .state_dict import StateDict
@@ -24,5 +25,7 @@ __all__ = [
     "RNGState",
     "NonFiniteStateError",
     "find_nonfinite",
+    "ReplicatedStateMismatchError",
+    "fingerprint_state",
     "__version__",
 ]

@@ -148,6 +148,22 @@ def get_nonfinite_policy() -> str:
     return policy
 
 
+def get_replicated_check_policy() -> str:
+    """What take()/async_take() do about state that is marked as replicated
+    but differs between ranks when their ``replicated_check`` argument is
+    None. "ignore" (default): nothing runs. "warn": fingerprint the
+    replicated leaves before the snapshot path is touched, compare across
+    ranks and log the leaves that differ. "error": raise
+    ReplicatedStateMismatchError on every rank instead of saving, leaving an
+    earlier snapshot at the path intact."""
+    policy = os.environ.get("TSAMD_REPLICATED_CHECK", "ignore")
+    if policy not in ("ignore", "warn", "error"):
+        raise ValueError(
+            f"TSAMD_REPLICATED_CHECK must be ignore|warn|error, got {policy}"
+        )
+    return policy
+
+
 def get_async_shadow_mode() -> str:
     """Shadow-clone async snapshots: "auto" (default) clones device
     tensors at HBM rate before async_take returns, when free HBM allows —

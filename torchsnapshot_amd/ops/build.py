@@ -24,6 +24,7 @@ DEPS = (
     PKG_ROOT / "ops" / "hip" / "desc_check.h",
     PKG_ROOT / "ops" / "hip" / "file_sink.h",
     PKG_ROOT / "ops" / "hip" / "table_ring.h",
+    Path(__file__).resolve(),  # the compiler flags
 )
 OUT = PKG_ROOT / f"_csnap{sysconfig.get_config_var('EXT_SUFFIX') or '.so'}"
 

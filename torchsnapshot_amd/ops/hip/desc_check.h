@@ -8,10 +8,10 @@
 // wu_prefix_of, grid_for, LaunchTables).
 //
 // Every entry point of the extension that takes descriptor rows -
-// pack_d2h, scatter_h2d, unpack_h2d, scan_nonfinite - runs check_descs
-// before it touches the GPU: a row that would make a kernel issue a
-// misaligned vector access, index past its rows, or wrap a u32 index is a
-// std::runtime_error here, not a device fault there.
+// pack_d2h, scatter_h2d, unpack_h2d, scan_nonfinite, fingerprint_tensors -
+// runs check_descs before it touches the GPU: a row that would make a
+// kernel issue a misaligned vector access, index past its rows, or wrap a
+// u32 index is a std::runtime_error here, not a device fault there.
 
 #pragma once
 
@@ -125,6 +125,8 @@ enum class DescKind {
   Scatter,  // scatter_h2d: plain byte scatter, no cast code
   Unpack,   // unpack_h2d: cast codes 0, 3, 4; needs a FlatSide
   Scan,     // scan_nonfinite: no cast code; needs one class per descriptor
+  Fingerprint,  // fingerprint_tensors: cast codes 0..2; flat_off is a hash
+                // offset and must be a multiple of vec
 };
 
 // unpack_h2d's flat side: where the payload sits and how long it is
@@ -153,7 +155,8 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
   const std::string who = kind == DescKind::Gather    ? "pack_d2h: "
                           : kind == DescKind::Scatter ? "scatter_h2d: "
                           : kind == DescKind::Unpack  ? "unpack_h2d: "
-                                                      : "scan_nonfinite: ";
+                          : kind == DescKind::Scan    ? "scan_nonfinite: "
+                                                      : "fingerprint_tensors: ";
   auto refuse = [&who](const char* what) {
     throw std::runtime_error(who + what);
   };
@@ -188,6 +191,11 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
         if ((*classes)[i] >= kScanClasses) refuse("unknown element class");
         if (cast) refuse("cast descriptors not allowed");
         break;
+      case DescKind::Fingerprint:
+        if (d.cast > kCastF16) {
+          refuse("widening cast descriptors are scatter-only (unpack_h2d)");
+        }
+        break;
     }
     if (d.nbytes == 0) continue;
     if (d.nbytes > kMaxDescBytes) {
@@ -213,13 +221,20 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
     if (kind == DescKind::Unpack && (flat->pinned_ptr + d.flat_off) % v != 0) {
       refuse("flat address not aligned for its vec");
     }
+    if (kind == DescKind::Fingerprint && d.flat_off % v != 0) {
+      // a 16-byte piece must cover exactly two words of the hash, a
+      // narrower one must stay inside one
+      refuse("flat_off not a multiple of vec");
+    }
     // the widest single access on the tensor side
     const unsigned long long align = !cast ? v : v == 16 ? 16 : 2ull * v;
+    // the two kinds whose kernels only load
+    const bool reads = kind == DescKind::Scan || kind == DescKind::Fingerprint;
     bool ok = reinterpret_cast<uintptr_t>(d.tensor_base) % align == 0;
     unsigned long long rows = 1;
     for (uint32_t k = 0; k < d.ndim; ++k) {
       ok = ok && (unsigned long long)d.strides[k] % align == 0;
-      if (kind == DescKind::Scan) {
+      if (reads) {
         // loads only ever land inside the rows the descriptor names
         ok = ok && d.strides[k] >= 0 && d.sizes[k] != 0;
       }
@@ -229,7 +244,7 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
       refuse(cast ? "cast descriptor: tensor side not aligned for its vec"
                   : "tensor not aligned for its vec");
     }
-    if (kind == DescKind::Scan && d.ndim != 0 &&
+    if (reads && d.ndim != 0 &&
         rows * d.row_bytes != d.nbytes) {
       refuse("sizes do not cover nbytes");
     }

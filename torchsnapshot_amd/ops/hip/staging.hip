@@ -13,6 +13,8 @@
 //     f32 widening and the psum64 check fused into the launch
 //   - scan kernel: NaN / Inf counts per tensor over the same descriptors,
 //     read-only, one launch for the whole state (the nonfinite= policy)
+//   - fingerprint kernel: the psum64 of each tensor's stored bytes, read in
+//     place over the same descriptors (the replicated_check= policy)
 //   - SDMA copies (hipMemcpyAsync) slab <-> pinned host memory; the slab
 //     can also be skipped entirely ("direct" mode): the kernel writes
 //     gathered bytes straight into pinned host memory over PCIe
@@ -26,7 +28,9 @@
 //     with (flat index, tensor address). TS = tensor bytes per flat byte:
 //     1 for copy, scatter and scan, 2 for cast and widen
 //   - lane operations: copy_vec (+ psum_contrib), cast_vec, scatter_vec,
-//     widen_vec, scan_vec. Each kernel family differs only in this
+//     widen_vec, scan_vec; the fingerprint's is psum_contrib alone, or
+//     cast_regs + psum_regs, the register half of cast_vec. Each kernel
+//     family differs only in this
 //   - add_per_wave: wave64 reduction and one atomic per wave, for the u64
 //     hashes and the u32 counters alike
 //   - on the host (desc_check.h): parse_descs + check_descs validate every
@@ -382,56 +386,69 @@ __device__ inline uint32_t cast_pair(uint32_t lo, uint32_t hi, uint32_t code) {
   return f32_to_f16_bits(lo) | (f32_to_f16_bits(hi) << 16);
 }
 
-// Convert 2*VEC source bytes at `src` into VEC bytes at `flat`. Every load
-// and store is naturally aligned to its own width (the host picks vec so).
-// When HASH, returns the psum64 contribution of the STORED bytes.
-template <int VEC, bool HASH>
-__device__ inline unsigned long long cast_vec(char* flat, const char* src,
-                                              uint32_t code,
-                                              unsigned long long file_off) {
-  unsigned long long h = 0;
+// The register part of the narrowing, shared by the gather and the
+// fingerprint: read 2*VEC source bytes at `src` and return the VEC stored
+// bytes packed little-endian in the low words of a uint4 (x | y | z | w;
+// at VEC 2 the low half of x). Every load is naturally aligned to its own
+// width (the host picks vec so).
+template <int VEC>
+__device__ inline uint4 cast_regs(const char* src, uint32_t code) {
+  uint4 o = make_uint4(0u, 0u, 0u, 0u);
   if (VEC == 16) {
     const uint4 a = *reinterpret_cast<const uint4*>(src);
     const uint4 b = *reinterpret_cast<const uint4*>(src + 16);
-    uint4 o;
     o.x = cast_pair(a.x, a.y, code);
     o.y = cast_pair(a.z, a.w, code);
     o.z = cast_pair(b.x, b.y, code);
     o.w = cast_pair(b.z, b.w, code);
-    *reinterpret_cast<uint4*>(flat) = o;
-    if (HASH) {
-      unsigned long long w = file_off >> 3;
-      h += (((unsigned long long)o.y << 32) | o.x) * psum_mult(w);
-      h += (((unsigned long long)o.w << 32) | o.z) * psum_mult(w + 1);
-    }
   } else if (VEC == 8) {
     const uint4 a = *reinterpret_cast<const uint4*>(src);
-    uint2 o;
     o.x = cast_pair(a.x, a.y, code);
     o.y = cast_pair(a.z, a.w, code);
-    *reinterpret_cast<uint2*>(flat) = o;
-    if (HASH) {
-      h += (((unsigned long long)o.y << 32) | o.x) * psum_mult(file_off >> 3);
-    }
   } else if (VEC == 4) {
     const uint2 a = *reinterpret_cast<const uint2*>(src);
-    const uint32_t o = cast_pair(a.x, a.y, code);
-    *reinterpret_cast<uint32_t*>(flat) = o;
-    if (HASH) {
-      h += ((unsigned long long)o << (8 * (file_off & 7))) *
-           psum_mult(file_off >> 3);
-    }
+    o.x = cast_pair(a.x, a.y, code);
   } else {
     const uint32_t a = *reinterpret_cast<const uint32_t*>(src);
-    const uint32_t o = (code == kCastBF16 ? f32_to_bf16_bits(a)
-                                          : f32_to_f16_bits(a)) & 0xFFFFu;
-    *reinterpret_cast<uint16_t*>(flat) = (uint16_t)o;
-    if (HASH) {
-      h += ((unsigned long long)o << (8 * (file_off & 7))) *
-           psum_mult(file_off >> 3);
-    }
+    o.x = (code == kCastBF16 ? f32_to_bf16_bits(a) : f32_to_f16_bits(a)) &
+          0xFFFFu;
   }
-  return h;
+  return o;
+}
+
+// psum64 contribution of the VEC stored bytes cast_regs returned
+template <int VEC>
+__device__ inline unsigned long long psum_regs(const uint4& o,
+                                               unsigned long long file_off) {
+  if (VEC == 16) {
+    const unsigned long long w = file_off >> 3;
+    return (((unsigned long long)o.y << 32) | o.x) * psum_mult(w) +
+           (((unsigned long long)o.w << 32) | o.z) * psum_mult(w + 1);
+  }
+  if (VEC == 8) {
+    return (((unsigned long long)o.y << 32) | o.x) * psum_mult(file_off >> 3);
+  }
+  return ((unsigned long long)o.x << (8 * (file_off & 7))) *
+         psum_mult(file_off >> 3);
+}
+
+// Convert 2*VEC source bytes at `src` into VEC bytes at `flat`; the store
+// is naturally aligned to its own width. When HASH, returns the psum64
+// contribution of the STORED bytes.
+template <int VEC, bool HASH>
+__device__ inline unsigned long long cast_vec(char* flat, const char* src,
+                                              uint32_t code,
+                                              unsigned long long file_off) {
+  const uint4 o = cast_regs<VEC>(src, code);
+  if (VEC == 16)
+    *reinterpret_cast<uint4*>(flat) = o;
+  else if (VEC == 8)
+    *reinterpret_cast<uint2*>(flat) = make_uint2(o.x, o.y);
+  else if (VEC == 4)
+    *reinterpret_cast<uint32_t*>(flat) = o.x;
+  else
+    *reinterpret_cast<uint16_t*>(flat) = (uint16_t)o.x;
+  return HASH ? psum_regs<VEC>(o, file_off) : 0ull;
 }
 
 // Cast counterpart of gather_range: [s, e) is in destination (flat-side)
@@ -778,6 +795,115 @@ __global__ __launch_bounds__(kBlockThreads) void scan_kernel(
         add_per_wave(&counts[2 * owner], nan);
         add_per_wave(&counts[2 * owner + 1], inf);
       });
+}
+
+// ---------------------------------------------------------------------------
+// fingerprint: the psum64 of each descriptor's STORED bytes in logical
+// (row-major) order, as if they began at file offset flat_off, read in
+// place from the strided tensor. Nothing is staged and nothing is stored
+// but one u64 per descriptor. With flat_off = 0 the value is the host
+// psum64 of t.contiguous()'s bytes (of t.to(stored).contiguous()'s under a
+// cast code), whatever the tensor's strides: the flat index the traversal
+// hands the lane operation is the byte's position in that contiguous image,
+// and the contribution rule (psum_mult of the word index, narrow pieces
+// shifted into their word lane) is the gather's.
+//
+//   - driver and traversal: for_each_work_unit and for_each_vec, like every
+//     other kernel here; the gather's descriptors describe the tensor, so
+//     the work split (64 KiB of stored bytes per workgroup pass, lanes
+//     across a contiguous run or a wide row, one lane per narrow row) is
+//     the gather's and the scan's. The grid is capped lower than theirs,
+//     at 2048 workgroups (see the launcher)
+//   - plain descriptors (TS = 1): one naturally aligned VEC-byte load and
+//     psum_contrib of the registers it filled
+//   - cast descriptors, codes 1 and 2 (TS = 2): the lane reads 2*VEC bytes
+//     of f32, narrows them with cast_regs - the conversion the gather
+//     stores - and hashes the packed result with psum_regs. Nothing is
+//     written, so the value is the hash of what a save_dtype gather would
+//     store, NaN quieting and overflow to inf included
+//   - load scheduling: the kernel is a pure HBM read; per 64-bit word it
+//     pays the two multiplies of splitmix64 and the one by the weight. The
+//     multiplier is a function of the flat index alone, never of loaded
+//     data, so it sits off the load's dependency chain; the contiguous loop
+//     is unrolled by 4 (as scan_range's is), which puts four independent
+//     loads in flight per lane while the multipliers of those four words
+//     are computed. Each lane keeps one u64 accumulator
+//   - reduction: the lane sums are carried from one work unit to the next
+//     while the workgroup stays on one descriptor, and add_per_wave issues
+//     one atomic per wave each time it moves on. Unlike the scan's
+//     counters, which are zero on healthy state and then issue no atomic,
+//     every wave here has a sum to add, and all waves of a tensor add to
+//     one address: the fewer atomics, the better
+//     (profiles/replicated_check_measurements.md)
+//   - determinism: every step - the lane sums, the wave reduction, the
+//     atomics - is wrapping u64 addition, which is associative and
+//     commutative. The result is therefore bit-exact for any grid size,
+//     any unroll and any order in which the atomics land. The cross-rank
+//     comparison of replicated state rests on this: equal bytes give equal
+//     fingerprints on every rank, always
+//
+// check_descs (DescKind::Fingerprint) keeps every load inside the rows the
+// descriptor names and requires flat_off % vec == 0, so that no piece
+// straddles a word of the hash (a 16-byte piece covers exactly two).
+// ---------------------------------------------------------------------------
+
+// Fingerprint counterpart of gather_range / cast_range: this thread's
+// psum64 contribution over [s, e) of the stored bytes of one work unit.
+template <int VEC, int TS>
+__device__ __forceinline__ unsigned long long fingerprint_range(
+    const Desc& d, uint32_t s, uint32_t e) {
+  const unsigned long long off0 = d.flat_off;
+  const uint32_t code = d.cast;
+  unsigned long long h = 0;
+  for_each_vec<VEC, TS, 4>(d, s, e, [&](unsigned long long i, const char* src) {
+    if constexpr (TS == 2) {
+      h += psum_regs<VEC>(cast_regs<VEC>(src, code), off0 + i);
+    } else {
+      h += psum_contrib<VEC>(src, off0 + i);
+    }
+  });
+  return h;
+}
+
+// out[i]: fingerprint of descriptor i (zeroed by the launcher)
+__global__ __launch_bounds__(kBlockThreads) void fingerprint_kernel(
+    const Desc* __restrict__ descs, int n,
+    const unsigned long long* __restrict__ wu_prefix,
+    unsigned long long total_wus, unsigned long long* __restrict__ out) {
+  // The lane sums are carried from one work unit to the next for as long
+  // as the workgroup stays with the same descriptor (the owner is uniform
+  // across the workgroup), and reduced when it moves on: a large tensor
+  // costs each wave one atomic, not one per work unit.
+  unsigned long long acc = 0;
+  int cur = -1;
+  for_each_work_unit(
+      descs, n, wu_prefix, total_wus,
+      [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
+        if (owner != cur) {
+          if (cur >= 0) add_per_wave(&out[cur], acc);
+          acc = 0;
+          cur = owner;
+        }
+        unsigned long long h = 0;
+        if (d.cast != kCastNone) {
+          switch (d.vec) {
+            case 16: h = fingerprint_range<16, 2>(d, s, e); break;
+            case 8: h = fingerprint_range<8, 2>(d, s, e); break;
+            case 4: h = fingerprint_range<4, 2>(d, s, e); break;
+            default: h = fingerprint_range<2, 2>(d, s, e); break;
+          }
+        } else {
+          switch (d.vec) {
+            case 16: h = fingerprint_range<16, 1>(d, s, e); break;
+            case 8: h = fingerprint_range<8, 1>(d, s, e); break;
+            case 4: h = fingerprint_range<4, 1>(d, s, e); break;
+            case 2: h = fingerprint_range<2, 1>(d, s, e); break;
+            default: h = fingerprint_range<1, 1>(d, s, e); break;
+          }
+        }
+        acc += h;
+      });
+  if (cur >= 0) add_per_wave(&out[cur], acc);
 }
 
 // ---------------------------------------------------------------------------
@@ -1271,6 +1397,74 @@ static std::vector<unsigned long long> scan_nonfinite(
   return counts;
 }
 
+// ---------------------------------------------------------------------------
+// fingerprints of N strided device tensors in one launch (blocking).
+// `flat` holds gather-style descriptor rows (cast codes 0..2); flat_off is
+// the file offset the descriptor's first stored byte is hashed at. Returns
+// one psum64 per descriptor.
+// ---------------------------------------------------------------------------
+
+static std::vector<unsigned long long> fingerprint_tensors(
+    const std::vector<unsigned long long>& flat, int n,
+    uintptr_t producer_stream, int device) {
+  // refused before the GPU is touched
+  const std::vector<Desc> descs = parse_descs(flat, n);
+  check_descs(descs, DescKind::Fingerprint);
+  std::vector<unsigned long long> sums((size_t)n, 0);
+
+  const std::vector<unsigned long long> wu_prefix = wu_prefix_of(descs);
+  const unsigned long long total_wus = wu_prefix[n];
+  if (total_wus == 0) return sums;
+
+  // one device allocation: descriptors | prefix sums | sums
+  const LaunchTables tables(descs, wu_prefix);
+  const size_t sum_bytes = sizeof(unsigned long long) * n;
+
+  // HBM-bound read. 2048 workgroups fill all 8 XCDs and keep a workgroup
+  // on one large tensor for many work units, so that its sums are carried
+  // and not added atomically; many small tensors are indifferent to the
+  // cap (grid sweep in profiles/replicated_check_measurements.md)
+  const unsigned int grid =
+      grid_for(total_wus, 2048ull, getenv("TSAMD_PACK_GRID"));
+
+  py::gil_scoped_release release;
+  HIP_CHECK(hipSetDevice(device));
+  DeviceCtx& ctx = get_ctx(device);
+  hipStream_t stream = ctx.d2h_stream;
+  chain_after(stream, producer_stream, device);
+
+  void* scratch = nullptr;
+  HIP_CHECK(hipMallocAsync(&scratch, tables.host.size() + sum_bytes, stream));
+  unsigned long long* d_sums = reinterpret_cast<unsigned long long*>(
+      reinterpret_cast<char*>(scratch) + tables.host.size());
+
+  // enqueue everything, then synchronise whatever happened: the host
+  // buffers above must outlive the copies that read and write them
+  hipError_t err = hipMemsetAsync(d_sums, 0, sum_bytes, stream);
+  if (err == hipSuccess) {
+    err = hipMemcpyAsync(scratch, tables.host.data(), tables.host.size(),
+                         hipMemcpyHostToDevice, stream);
+  }
+  if (err == hipSuccess) {
+    hipLaunchKernelGGL(fingerprint_kernel, dim3(grid), dim3(kBlockThreads), 0,
+                       stream, tables.descs(scratch), n,
+                       tables.prefix(scratch), total_wus, d_sums);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess) {
+    err = hipMemcpyAsync(sums.data(), d_sums, sum_bytes, hipMemcpyDeviceToHost,
+                         stream);
+  }
+  (void)hipFreeAsync(scratch, stream);
+  const hipError_t sync_err = hipStreamSynchronize(stream);
+  if (err == hipSuccess) err = sync_err;
+  if (err != hipSuccess) {
+    throw std::runtime_error(std::string("fingerprint_tensors: ") +
+                             hipGetErrorString(err));
+  }
+  return sums;
+}
+
 // Host-side psum64 (single pass, std::thread-parallel): the
 // python-level vectorized implementations burn ~10 full memory passes
 // on splitmix temporaries (~0.2-0.3 GB/s); this one runs at memcpy-ish
@@ -1479,6 +1673,12 @@ PYBIND11_MODULE(_csnap, m) {
         "(blocking); returns [nan_0, inf_0, nan_1, inf_1, ...]",
         py::arg("flat"), py::arg("classes"), py::arg("n"),
         py::arg("producer_stream"), py::arg("device"));
+  m.def("fingerprint_tensors", &fingerprint_tensors,
+        "psum64 of the stored bytes of strided device tensors, read in place "
+        "in one launch (blocking); one value per descriptor, hashed at file "
+        "offset flat_off",
+        py::arg("flat"), py::arg("n"), py::arg("producer_stream"),
+        py::arg("device"));
   m.def("file_write", &::file_write,  // not tsamd::file_write
        
         "write a buffer to a file (GIL released); reuse=True overwrites an "

@@ -576,6 +576,107 @@ def torch_count_nonfinite(
     return int(torch.isnan(view).sum()), int(torch.isinf(view).sum())
 
 
+# ---------------------------------------------------------------------------
+# fingerprint descriptors
+# ---------------------------------------------------------------------------
+
+
+def build_fingerprint_items(
+    tensors: Sequence[torch.Tensor],
+    stored_dtypes: Optional[Sequence[Optional[torch.dtype]]] = None,
+    split_bytes: Optional[int] = None,
+) -> List[Optional[List[PackItem]]]:
+    """Fingerprint-kernel descriptors for a batch, one entry per tensor.
+
+    They are the gather's descriptors (cast ones for a float32 tensor
+    stored as bfloat16/float16) with ``flat_offset`` turned into the byte
+    offset at which the piece is hashed: 0 for a whole tensor. A tensor
+    whose stored size reaches ``split_bytes`` (default: the kernel's cap)
+    is cut along dim 0 into pieces at cumulative stored offsets, with vec
+    reduced to divide the offset; psum64 is additive over disjoint byte
+    ranges, so the piece sums add up (mod 2^64) to the whole tensor's. An
+    entry is ``[]`` for a tensor without elements and None when the builder
+    declines and the caller hashes on the host: a quantized or sparse
+    tensor, a lazy conjugate or negative view (descriptors state raw memory;
+    StagingEngine.fingerprint resolves those first), a stored dtype the
+    kernel cannot cast to, elements that are not aligned to their size, more
+    than MAX_OUTER_DIMS strided dims, or a tensor at the cap that dim 0
+    cannot split."""
+    if stored_dtypes is None:
+        stored_dtypes = [None] * len(tensors)
+    if len(stored_dtypes) != len(tensors):
+        raise ValueError("stored_dtypes must have one entry per tensor")
+    if split_bytes is None:
+        split_bytes = _KERNEL_MAX_BYTES
+    out: List[Optional[List[PackItem]]] = []
+    for t, stored in zip(tensors, stored_dtypes):
+        if (
+            t.is_quantized
+            or t.layout != torch.strided
+            or t.is_conj()
+            or t.is_neg()
+        ):
+            out.append(None)
+            continue
+        t = t.detach()
+        if stored == t.dtype:
+            stored = None
+        if (
+            (stored is not None and (t.dtype, stored) not in _CAST_CODES)
+            or t.data_ptr() % t.element_size()
+        ):
+            out.append(None)
+            continue
+        if t.numel() == 0:
+            out.append([])
+            continue
+        stored_esz = (stored or t.dtype).itemsize
+        pieces = [t]
+        if t.numel() * stored_esz >= split_bytes:
+            row_bytes = t.numel() * stored_esz // t.shape[0] if t.dim() else 0
+            rows = split_bytes // row_bytes if row_bytes else 0
+            if rows == 0:
+                out.append(None)
+                continue
+            pieces = [
+                t.narrow(0, r, min(rows, t.shape[0] - r))
+                for r in range(0, t.shape[0], rows)
+            ]
+        if any(outer_dim_count(p) > MAX_OUTER_DIMS for p in pieces):
+            out.append(None)
+            continue
+        items, _, _ = build_pack_items(pieces, [stored] * len(pieces))
+        off = 0
+        for it in items:
+            it.flat_offset = off
+            it.vec = math.gcd(it.vec, off) if off else it.vec
+            off += it.nbytes
+        out.append(items)
+    return out
+
+
+def host_fingerprint(
+    t: torch.Tensor, stored_dtype: Optional[torch.dtype] = None
+) -> int:
+    """psum64 of the bytes ``t`` is stored as, computed on the host: what
+    the fingerprint kernel must agree with, and the path for host tensors
+    and for anything build_fingerprint_items() declines."""
+    from ..integrity import psum64_value
+
+    t = t.detach()
+    if t.is_quantized:
+        t = t.int_repr()
+    if t.layout != torch.strided:
+        t = t.to_dense()
+    t = resolve_lazy(t)
+    if stored_dtype is not None:
+        t = t.to(stored_dtype)
+    if t.numel() == 0:
+        return 0
+    flat = t.contiguous().cpu().reshape(-1).view(torch.uint8)
+    return psum64_value(flat.numpy())
+
+
 def _items_to_flat(items: List[PackItem]) -> List[int]:
     """Serialize descriptors for the extension: fixed-width int rows."""
     MAXD = 6
@@ -1101,6 +1202,64 @@ class StagingEngine:
                     torch_count_nonfinite(tensors[i], stored_dtypes[i])
                 )
         return [(a, b) for a, b in out]
+
+    # -- fingerprint --------------------------------------------------------
+
+    def fingerprint(
+        self,
+        tensors: Sequence[torch.Tensor],
+        stored_dtypes: Optional[Sequence[Optional[torch.dtype]]] = None,
+        split_bytes: Optional[int] = None,
+    ) -> List[int]:
+        """psum64 of the bytes each of this device's ``tensors`` is stored
+        as, from ONE read-only fingerprint-kernel launch over all of them:
+        nothing is staged. Blocking.
+
+        The value equals ``integrity.psum64_value`` of
+        ``t.contiguous()``'s bytes (of ``t.to(stored).contiguous()``'s with
+        ``stored_dtypes[i]`` bfloat16/float16 for a float32 tensor) and does
+        not depend on the tensor's strides. It is a comparison of bytes:
+        NaN payloads and the sign of zero count.
+
+        Tensors build_fingerprint_items() declines are hashed on the host
+        instead; so is everything when the extension is disabled by
+        TSAMD_DISABLE_HIP_STAGING=1. ``split_bytes`` overrides the stored
+        size from which a tensor is hashed in dim-0 pieces."""
+        if stored_dtypes is None:
+            stored_dtypes = [None] * len(tensors)
+        if not self._use_ext:
+            return [
+                host_fingerprint(t, st) for t, st in zip(tensors, stored_dtypes)
+            ]
+        # descriptors state raw memory: lazy views are hashed by value, as
+        # they are saved. The resolved copies live until the launch returns
+        tensors = [
+            t if t.is_quantized or t.layout != torch.strided else resolve_lazy(t)
+            for t in tensors
+        ]
+        per_tensor = build_fingerprint_items(tensors, stored_dtypes, split_bytes)
+        flat_items: List[PackItem] = []
+        owners: List[int] = []
+        for i, its in enumerate(per_tensor):
+            for it in its or ():
+                flat_items.append(it)
+                owners.append(i)
+        out = [0] * len(tensors)
+        if flat_items:
+            dev_index = self.device.index or 0
+            with torch.cuda.device(dev_index):
+                sums = _csnap.fingerprint_tensors(
+                    _items_to_flat(flat_items),
+                    len(flat_items),
+                    torch.cuda.current_stream().cuda_stream,
+                    dev_index,
+                )
+            for k, i in enumerate(owners):
+                out[i] = (out[i] + int(sums[k])) % (1 << 64)
+        for i, its in enumerate(per_tensor):
+            if its is None:
+                out[i] = host_fingerprint(tensors[i], stored_dtypes[i])
+        return out
 
     # -- debug fallback -----------------------------------------------------
 

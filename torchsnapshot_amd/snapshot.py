@@ -32,7 +32,7 @@ from typing import Any, Dict, List, Optional, Set, Tuple, Union
 import torch
 import torch.distributed as dist
 
-from . import knobs, nonfinite as _nonfinite
+from . import knobs, nonfinite as _nonfinite, replication as _replication
 from .dist_store import LinearBarrier, get_or_create_store
 from .event import Event, log_event
 from .flatten import Flattened, flatten, inflate
@@ -241,6 +241,7 @@ class Snapshot:
         _custom_tensor_prepare_func: Optional[Any] = None,
         save_dtype: SaveDtype = None,
         nonfinite: Optional[str] = None,
+        replicated_check: Optional[str] = None,
     ) -> "Snapshot":
         """``save_dtype``: store float32 tensors narrowed to
         ``torch.bfloat16`` / ``torch.float16`` — one dtype for everything,
@@ -254,11 +255,22 @@ class Snapshot:
         before anything under ``path`` is touched. ``"error"`` raises
         :class:`NonFiniteStateError` on every rank and leaves an earlier
         snapshot at ``path`` intact; ``"warn"`` logs the offending leaves
-        and saves."""
+        and saves.
+
+        ``replicated_check``: ``"ignore" | "warn" | "error"``, or None for
+        the ``TSAMD_REPLICATED_CHECK`` knob (default ignore). Other than
+        ignore, with more than one rank, every plain tensor leaf that is
+        marked as replicated is fingerprinted as it will be stored and the
+        fingerprints are compared across ranks before anything under
+        ``path`` is touched. ``"error"`` raises
+        :class:`ReplicatedStateMismatchError` on every rank when a leaf
+        differs and leaves an earlier snapshot at ``path`` intact;
+        ``"warn"`` logs the leaves and saves."""
         torch._C._log_api_usage_once("torchsnapshot_amd.Snapshot.take")
         cls._validate_app_state(app_state)
         save_dtype_rules = _normalize_save_dtype(save_dtype)
         nonfinite_policy = _nonfinite.resolve_policy(nonfinite)
+        replicated_policy = _replication.resolve_policy(replicated_check)
         pg_wrapper = PGWrapper(pg)
         unique_id = uuid.uuid4().hex
         event_meta = {"id": unique_id, "rank": pg_wrapper.get_rank(), "api": "take"}
@@ -279,6 +291,7 @@ class Snapshot:
                     custom_tensor_prepare_func=_custom_tensor_prepare_func,
                     save_dtype_rules=save_dtype_rules,
                     nonfinite_policy=nonfinite_policy,
+                    replicated_policy=replicated_policy,
                 )
                 pending_io_work.complete()
                 from .integrity import write_checksum_file
@@ -308,14 +321,17 @@ class Snapshot:
         _custom_tensor_prepare_func: Optional[Any] = None,
         save_dtype: SaveDtype = None,
         nonfinite: Optional[str] = None,
+        replicated_check: Optional[str] = None,
     ) -> "PendingSnapshot":
-        """See :meth:`take` for ``save_dtype`` and ``nonfinite``; a
-        :class:`NonFiniteStateError` is raised here, not by the pending
-        snapshot."""
+        """See :meth:`take` for ``save_dtype``, ``nonfinite`` and
+        ``replicated_check``; a :class:`NonFiniteStateError` or
+        :class:`ReplicatedStateMismatchError` is raised here, not by the
+        pending snapshot."""
         torch._C._log_api_usage_once("torchsnapshot_amd.Snapshot.async_take")
         cls._validate_app_state(app_state)
         save_dtype_rules = _normalize_save_dtype(save_dtype)
         nonfinite_policy = _nonfinite.resolve_policy(nonfinite)
+        replicated_policy = _replication.resolve_policy(replicated_check)
         pg_wrapper = PGWrapper(pg)
         unique_id = uuid.uuid4().hex
         event_meta = {
@@ -350,6 +366,7 @@ class Snapshot:
                 custom_tensor_prepare_func=_custom_tensor_prepare_func,
                 save_dtype_rules=save_dtype_rules,
                 nonfinite_policy=nonfinite_policy,
+                replicated_policy=replicated_policy,
             )
             # once staging is complete, the app may mutate its state
             # freely. With shadow clones (sources_immutable) there is
@@ -390,6 +407,7 @@ class Snapshot:
         custom_tensor_prepare_func: Optional[Any] = None,
         save_dtype_rules: Optional[List[Tuple[str, torch.dtype]]] = None,
         nonfinite_policy: str = "ignore",
+        replicated_policy: str = "ignore",
     ) -> Tuple[PendingIOWork, SnapshotMetadata]:
         rank = pg_wrapper.get_rank()
         world_size = pg_wrapper.get_world_size()
@@ -449,6 +467,22 @@ class Snapshot:
                 nonfinite_policy,
                 _nonfinite.scan_leaves(
                     flattened,
+                    lambda p, obj: _resolve_save_dtype(save_dtype_rules, p, obj),
+                ),
+                pg_wrapper,
+            )
+
+        # replicated check: the leaves below are about to be written by one
+        # rank and dropped by the others on the claim that they are equal
+        # everywhere. Fingerprint what each rank would store and compare,
+        # at the same point and for the same reason as the scan above: a
+        # refusal leaves an earlier commit at the path intact.
+        if replicated_policy != "ignore" and world_size > 1 and replicated_paths:
+            _replication.enforce(
+                replicated_policy,
+                _replication.fingerprint_leaves(
+                    flattened,
+                    replicated_paths,
                     lambda p, obj: _resolve_save_dtype(save_dtype_rules, p, obj),
                 ),
                 pg_wrapper,
