@@ -15,18 +15,17 @@ more is an Inf once stored as float16.
 from __future__ import annotations
 
 import logging
-from typing import Any, Callable, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
-from . import knobs
-from .flatten import flatten
+from . import knobs, state_checks
 from .pg_wrapper import PGWrapper
 from .stateful import AppState
 
 logger = logging.getLogger(__name__)
 
-POLICIES = ("ignore", "warn", "error")
+POLICIES = state_checks.POLICIES
 
 # {logical_path: (nan, inf)} for one rank; with the rank appended once
 # findings have been exchanged
@@ -60,53 +59,33 @@ def _describe(report: Report, limit: int = 5) -> str:
 def resolve_policy(nonfinite: Optional[str]) -> str:
     """The policy of one take() call: the argument, or the TSAMD_NONFINITE
     knob when it is None. Anything else raises ValueError."""
-    if nonfinite is None:
-        return knobs.get_nonfinite_policy()
-    if nonfinite not in POLICIES:
-        raise ValueError(
-            f"nonfinite must be one of {'|'.join(POLICIES)} or None, "
-            f"got {nonfinite!r}"
-        )
-    return nonfinite
+    return state_checks.resolve_policy(
+        nonfinite, "nonfinite", knobs.get_nonfinite_policy
+    )
 
 
 def _local_tensors(obj: Any) -> List[torch.Tensor]:
     """The plain local tensors behind one flattened leaf."""
     if not isinstance(obj, torch.Tensor):
         return []
-    try:
-        from torch.distributed.tensor import DTensor
-
-        if isinstance(obj, DTensor):
-            return [obj.to_local()]
-    except ImportError:
-        pass
-    try:
-        from torch.distributed._shard.sharded_tensor import ShardedTensor
-
-        if isinstance(obj, ShardedTensor):
-            return [s.tensor for s in obj.local_shards()]
-    except ImportError:
-        pass
-    if type(obj) is torch.Tensor or isinstance(obj, torch.nn.Parameter):
+    if state_checks.is_dtensor(obj):
+        return [obj.to_local()]
+    if state_checks.is_sharded_tensor(obj):
+        return [s.tensor for s in obj.local_shards()]
+    if state_checks.is_plain_tensor(obj):
         return [obj.detach()]
     return []
 
 
 def scan_leaves(
-    flattened: Dict[str, Any],
-    resolve_stored: Callable[[str, Any], Optional[torch.dtype]],
+    flattened: Dict[str, Any], resolve_stored: state_checks.ResolveStored
 ) -> LocalReport:
     """Count NaN and Inf in every float tensor leaf of ``flattened`` and
     return the offending ones. ``resolve_stored(path, leaf)`` names the
     dtype a leaf will be stored as (None = its own). Aliased leaves (tied
     weights) are scanned once and reported under every path."""
-    from .ops import staging
-
     # unique tensors to scan, and which of them each path is made of
-    keys: Dict[Any, int] = {}
-    tensors: List[torch.Tensor] = []
-    stored: List[Optional[torch.dtype]] = []
+    unique = state_checks.UniqueTensors()
     members: Dict[str, List[int]] = {}
     for path, obj in flattened.items():
         locals_ = _local_tensors(obj)
@@ -121,35 +100,9 @@ def scan_leaves(
                 or t.device.type == "meta"
             ):
                 continue
-            key = (
-                t.data_ptr(),
-                t.dtype,
-                tuple(t.shape),
-                tuple(t.stride()),
-                str(t.device),
-                stored_dtype,
-            )
-            if key not in keys:
-                keys[key] = len(tensors)
-                tensors.append(t)
-                stored.append(stored_dtype)
-            members.setdefault(path, []).append(keys[key])
+            members.setdefault(path, []).append(unique.add(t, stored_dtype))
 
-    counts: List[Tuple[int, int]] = [(0, 0)] * len(tensors)
-    by_device: Dict[int, List[int]] = {}
-    for i, t in enumerate(tensors):
-        if t.device.type == "cuda":
-            by_device.setdefault(t.device.index or 0, []).append(i)
-        else:
-            counts[i] = staging.torch_count_nonfinite(t, stored[i])
-    for dev_index, idxs in by_device.items():
-        engine = staging.get_staging_engine(torch.device("cuda", dev_index))
-        got = engine.scan_nonfinite(
-            [tensors[i] for i in idxs], [stored[i] for i in idxs]
-        )
-        for i, c in zip(idxs, got):
-            counts[i] = c
-
+    counts = unique.read("torch_count_nonfinite", "scan_nonfinite")
     report: LocalReport = {}
     for path, idxs in members.items():
         nan = sum(counts[i][0] for i in idxs)
@@ -167,15 +120,9 @@ def enforce(
     "error" raises NonFiniteStateError everywhere, "warn" logs once per
     rank."""
     rank = pg_wrapper.get_rank()
-    world_size = pg_wrapper.get_world_size()
-    gathered: List[Optional[LocalReport]] = [None] * world_size
-    if world_size > 1:
-        pg_wrapper.all_gather_object(gathered, local)
-    else:
-        gathered[0] = local
     report: Report = {}
-    for r, found in enumerate(gathered):
-        for path, (nan, inf) in sorted((found or {}).items()):
+    for r, found in enumerate(state_checks.exchange(local, pg_wrapper)):
+        for path, (nan, inf) in sorted(found.items()):
             # one entry per path: the first offending rank's (a replicated
             # leaf is bad on every rank alike)
             report.setdefault(path, (nan, inf, r))
@@ -197,13 +144,4 @@ def find_nonfinite(
     without collectives: call it in a training loop before deciding to
     checkpoint. With ``save_dtype`` (as for take) the counts are those of
     the values as they would be stored. Complex leaves count components."""
-    from .snapshot import _normalize_save_dtype, _resolve_save_dtype
-
-    rules = _normalize_save_dtype(save_dtype)
-    flattened: Dict[str, Any] = {}
-    for key, stateful in app_state.items():
-        _, f = flatten(stateful.state_dict(), prefix=key)
-        flattened.update(f)
-    return scan_leaves(
-        flattened, lambda path, obj: _resolve_save_dtype(rules, path, obj)
-    )
+    return scan_leaves(*state_checks.flatten_app_state(app_state, save_dtype))

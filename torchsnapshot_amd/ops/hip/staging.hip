@@ -35,7 +35,9 @@
 //     hashes and the u32 counters alike
 //   - on the host (desc_check.h): parse_descs + check_descs validate every
 //     descriptor before the GPU is touched; wu_prefix_of, grid_for and
-//     LaunchTables are the launch prologue of both launchers
+//     LaunchTables are the launch prologue of both launchers: launch_pack
+//     for the copies, read_launch for the blocking read-only scan and
+//     fingerprint
 //   - on the host (table_ring.h): the launch tables reach the device
 //     through a ring of pinned slots, so a launch never waits for the
 //     stream it enqueues on, and the launch entry points hold no GIL
@@ -1178,6 +1180,60 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
   }
   return register_op(ev, device);
 }
+
+// The blocking launch of the entry points that read tensors in place and
+// bring a few words per descriptor back (scan_nonfinite,
+// fingerprint_tensors). Called with the GIL held, after everything that
+// needs it (argument conversion, the environment); releases it for all
+// GPU work. Runs on the D2H side stream, after the producer's. One device
+// allocation holds `tables` and `n_results` zeroed u64 behind them;
+// `launch(d_tables, d_results, stream)` enqueues the kernel. A HIP error
+// is thrown with `what` in front.
+template <typename Launch>
+std::vector<unsigned long long> read_launch(const LaunchTables& tables,
+                                            size_t n_results,
+                                            uintptr_t producer_stream,
+                                            int device, const char* what,
+                                            Launch launch) {
+  std::vector<unsigned long long> results(n_results, 0);
+  const size_t table_bytes = tables.host.size();
+  const size_t result_bytes = sizeof(unsigned long long) * n_results;
+
+  py::gil_scoped_release release;
+  HIP_CHECK(hipSetDevice(device));
+  DeviceCtx& ctx = get_ctx(device);
+  hipStream_t stream = ctx.d2h_stream;
+  chain_after(stream, producer_stream, device);
+
+  void* scratch = nullptr;
+  HIP_CHECK(hipMallocAsync(&scratch, table_bytes + result_bytes, stream));
+  unsigned long long* d_results = reinterpret_cast<unsigned long long*>(
+      static_cast<char*>(scratch) + table_bytes);
+
+  // enqueue everything, then synchronise whatever happened: the host
+  // buffers (`tables`, `results`) must outlive the copies that read and
+  // write them
+  hipError_t err = hipMemsetAsync(d_results, 0, result_bytes, stream);
+  if (err == hipSuccess) {
+    err = hipMemcpyAsync(scratch, tables.host.data(), table_bytes,
+                         hipMemcpyHostToDevice, stream);
+  }
+  if (err == hipSuccess) {
+    launch(scratch, d_results, stream);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess) {
+    err = hipMemcpyAsync(results.data(), d_results, result_bytes,
+                         hipMemcpyDeviceToHost, stream);
+  }
+  (void)hipFreeAsync(scratch, stream);
+  const hipError_t sync_err = hipStreamSynchronize(stream);
+  if (err == hipSuccess) err = sync_err;
+  if (err != hipSuccess) {
+    throw std::runtime_error(std::string(what) + hipGetErrorString(err));
+  }
+  return results;
+}
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1343,58 +1399,30 @@ static std::vector<unsigned long long> scan_nonfinite(
   // rows the descriptor names
   const std::vector<Desc> descs = parse_descs(flat, n);
   check_descs(descs, DescKind::Scan, nullptr, &classes);
-  std::vector<unsigned long long> counts(2 * (size_t)n, 0);
+  const size_t n_counts = 2 * (size_t)n;
 
   const std::vector<unsigned long long> wu_prefix = wu_prefix_of(descs);
   const unsigned long long total_wus = wu_prefix[n];
-  if (total_wus == 0) return counts;
+  if (total_wus == 0) return std::vector<unsigned long long>(n_counts, 0);
 
-  // one device allocation: descriptors | prefix sums | classes | counters
+  // descriptors | prefix sums | classes
   const LaunchTables tables(descs, wu_prefix, classes.data(),
                             sizeof(uint32_t) * n);
-  const size_t count_bytes = sizeof(unsigned long long) * 2 * n;
 
   // HBM-bound read: fill the chip like the slab-mode gather does
   const unsigned int grid =
       grid_for(total_wus, 16384ull, getenv("TSAMD_PACK_GRID"));
 
-  py::gil_scoped_release release;
-  HIP_CHECK(hipSetDevice(device));
-  DeviceCtx& ctx = get_ctx(device);
-  hipStream_t stream = ctx.d2h_stream;
-  chain_after(stream, producer_stream, device);
-
-  void* scratch = nullptr;
-  HIP_CHECK(hipMallocAsync(&scratch, tables.host.size() + count_bytes, stream));
-  unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(
-      reinterpret_cast<char*>(scratch) + tables.host.size());
-
-  // enqueue everything, then synchronise whatever happened: the host
-  // buffers above must outlive the copies that read and write them
-  hipError_t err = hipMemsetAsync(d_counts, 0, count_bytes, stream);
-  if (err == hipSuccess) {
-    err = hipMemcpyAsync(scratch, tables.host.data(), tables.host.size(),
-                         hipMemcpyHostToDevice, stream);
-  }
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(scan_kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
-                       tables.descs(scratch),
-                       static_cast<const uint32_t*>(tables.extra(scratch)), n,
-                       tables.prefix(scratch), total_wus, d_counts);
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess) {
-    err = hipMemcpyAsync(counts.data(), d_counts, count_bytes,
-                         hipMemcpyDeviceToHost, stream);
-  }
-  (void)hipFreeAsync(scratch, stream);
-  const hipError_t sync_err = hipStreamSynchronize(stream);
-  if (err == hipSuccess) err = sync_err;
-  if (err != hipSuccess) {
-    throw std::runtime_error(std::string("scan_nonfinite: ") +
-                             hipGetErrorString(err));
-  }
-  return counts;
+  return read_launch(
+      tables, n_counts, producer_stream, device, "scan_nonfinite: ",
+      [&](const void* d_tables, unsigned long long* d_counts,
+          hipStream_t stream) {
+        hipLaunchKernelGGL(
+            scan_kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
+            tables.descs(d_tables),
+            static_cast<const uint32_t*>(tables.extra(d_tables)), n,
+            tables.prefix(d_tables), total_wus, d_counts);
+      });
 }
 
 // ---------------------------------------------------------------------------
@@ -1410,15 +1438,13 @@ static std::vector<unsigned long long> fingerprint_tensors(
   // refused before the GPU is touched
   const std::vector<Desc> descs = parse_descs(flat, n);
   check_descs(descs, DescKind::Fingerprint);
-  std::vector<unsigned long long> sums((size_t)n, 0);
 
   const std::vector<unsigned long long> wu_prefix = wu_prefix_of(descs);
   const unsigned long long total_wus = wu_prefix[n];
-  if (total_wus == 0) return sums;
+  if (total_wus == 0) return std::vector<unsigned long long>((size_t)n, 0);
 
-  // one device allocation: descriptors | prefix sums | sums
+  // descriptors | prefix sums
   const LaunchTables tables(descs, wu_prefix);
-  const size_t sum_bytes = sizeof(unsigned long long) * n;
 
   // HBM-bound read. 2048 workgroups fill all 8 XCDs and keep a workgroup
   // on one large tensor for many work units, so that its sums are carried
@@ -1427,42 +1453,15 @@ static std::vector<unsigned long long> fingerprint_tensors(
   const unsigned int grid =
       grid_for(total_wus, 2048ull, getenv("TSAMD_PACK_GRID"));
 
-  py::gil_scoped_release release;
-  HIP_CHECK(hipSetDevice(device));
-  DeviceCtx& ctx = get_ctx(device);
-  hipStream_t stream = ctx.d2h_stream;
-  chain_after(stream, producer_stream, device);
-
-  void* scratch = nullptr;
-  HIP_CHECK(hipMallocAsync(&scratch, tables.host.size() + sum_bytes, stream));
-  unsigned long long* d_sums = reinterpret_cast<unsigned long long*>(
-      reinterpret_cast<char*>(scratch) + tables.host.size());
-
-  // enqueue everything, then synchronise whatever happened: the host
-  // buffers above must outlive the copies that read and write them
-  hipError_t err = hipMemsetAsync(d_sums, 0, sum_bytes, stream);
-  if (err == hipSuccess) {
-    err = hipMemcpyAsync(scratch, tables.host.data(), tables.host.size(),
-                         hipMemcpyHostToDevice, stream);
-  }
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(fingerprint_kernel, dim3(grid), dim3(kBlockThreads), 0,
-                       stream, tables.descs(scratch), n,
-                       tables.prefix(scratch), total_wus, d_sums);
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess) {
-    err = hipMemcpyAsync(sums.data(), d_sums, sum_bytes, hipMemcpyDeviceToHost,
-                         stream);
-  }
-  (void)hipFreeAsync(scratch, stream);
-  const hipError_t sync_err = hipStreamSynchronize(stream);
-  if (err == hipSuccess) err = sync_err;
-  if (err != hipSuccess) {
-    throw std::runtime_error(std::string("fingerprint_tensors: ") +
-                             hipGetErrorString(err));
-  }
-  return sums;
+  return read_launch(
+      tables, (size_t)n, producer_stream, device, "fingerprint_tensors: ",
+      [&](const void* d_tables, unsigned long long* d_sums,
+          hipStream_t stream) {
+        hipLaunchKernelGGL(fingerprint_kernel, dim3(grid),
+                           dim3(kBlockThreads), 0, stream,
+                           tables.descs(d_tables), n, tables.prefix(d_tables),
+                           total_wus, d_sums);
+      });
 }
 
 // Host-side psum64 (single pass, std::thread-parallel): the

@@ -27,7 +27,7 @@ import contextlib
 import math
 import threading
 from dataclasses import dataclass
-from typing import Dict, Iterator, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterator, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -207,6 +207,35 @@ def _layout_rows(
     return row_elems * flat_esz, sizes[:n_outer], outer_strides_b, src_align
 
 
+def _per_tensor_dtypes(
+    dtypes: Optional[Sequence[Optional[torch.dtype]]], n: int, name: str
+) -> Sequence[Optional[torch.dtype]]:
+    """An optional per-tensor stored-dtype argument as one entry per tensor
+    (None = stored as it is)."""
+    if dtypes is None:
+        return [None] * n
+    if len(dtypes) != n:
+        raise ValueError(f"{name} must have one entry per tensor")
+    return dtypes
+
+
+def _split_dim0(
+    t: torch.Tensor, nbytes: int, piece_bytes: int
+) -> Optional[List[torch.Tensor]]:
+    """``t``, of ``nbytes`` > 0 stored bytes, as dim-0 slices of at most
+    ``piece_bytes`` stored bytes each: the pieces of a tensor that is too
+    large for one descriptor of a read-only kernel. None when dim 0 cannot
+    cut it that small: a 0-dim tensor, or one row alone over
+    ``piece_bytes``."""
+    if t.dim() == 0 or nbytes // t.shape[0] > piece_bytes:
+        return None
+    rows = piece_bytes // (nbytes // t.shape[0])
+    return [
+        t.narrow(0, off, min(rows, t.shape[0] - off))
+        for off in range(0, t.shape[0], rows)
+    ]
+
+
 def build_pack_items(
     tensors: Sequence[torch.Tensor],
     out_dtypes: Optional[Sequence[Optional[torch.dtype]]] = None,
@@ -215,10 +244,7 @@ def build_pack_items(
     slab offsets, and total slab bytes (each tensor 256B-aligned).
     ``out_dtypes`` optionally names a stored dtype per tensor; the layout
     (offsets, sizes, total) is then in stored bytes."""
-    if out_dtypes is None:
-        out_dtypes = [None] * len(tensors)
-    if len(out_dtypes) != len(tensors):
-        raise ValueError("out_dtypes must have one entry per tensor")
+    out_dtypes = _per_tensor_dtypes(out_dtypes, len(tensors), "out_dtypes")
     items: List[PackItem] = []
     offsets: List[int] = []
     off = 0
@@ -484,7 +510,7 @@ def _build_scan_item(t: torch.Tensor) -> Optional[PackItem]:
     row_bytes, outer_sizes, outer_strides_b, src_align = _layout_rows(
         sizes, strides, esz, esz, t.data_ptr()
     )
-    if len(outer_sizes) > 6:
+    if len(outer_sizes) > MAX_OUTER_DIMS:
         return None
     vec = math.gcd(row_bytes, src_align)
     if vec < esz:
@@ -516,10 +542,7 @@ def build_scan_items(
     that splitting cannot bring under the cap. A complex tensor is
     described through ``torch.view_as_real``: its counts are of components.
     """
-    if stored_dtypes is None:
-        stored_dtypes = [None] * len(tensors)
-    if len(stored_dtypes) != len(tensors):
-        raise ValueError("stored_dtypes must have one entry per tensor")
+    stored_dtypes = _per_tensor_dtypes(stored_dtypes, len(tensors), "stored_dtypes")
     items: List[Optional[List[PackItem]]] = []
     classes: List[Optional[int]] = []
     for t, stored in zip(tensors, stored_dtypes):
@@ -529,35 +552,24 @@ def build_scan_items(
         if cls is None:
             items.append(None)
             continue
-        pieces = _split_for_scan(view)
+        nbytes = view.numel() * view.element_size()
+        if nbytes == 0:
+            items.append([])
+            continue
+        pieces: Optional[List[torch.Tensor]] = [view]
+        if nbytes > _KERNEL_MAX_BYTES:
+            # cut as the chunker would cut it
+            pieces = _split_dim0(
+                view,
+                nbytes,
+                min(knobs.get_max_chunk_size_bytes(), _KERNEL_MAX_BYTES),
+            )
         built = None if pieces is None else [_build_scan_item(p) for p in pieces]
         if built is None or any(it is None for it in built):
             items.append(None)
         else:
             items.append(built)
     return items, classes
-
-
-def _split_for_scan(t: torch.Tensor) -> Optional[List[torch.Tensor]]:
-    """``t`` as views of at most the scan cap each: itself, or dim-0 slices
-    of at most the chunk size as the chunker cuts them. None when one dim-0
-    row alone is over the cap."""
-    if t.numel() == 0:
-        return []
-    nbytes = t.numel() * t.element_size()
-    if nbytes <= _KERNEL_MAX_BYTES:
-        return [t]
-    if t.dim() == 0:
-        return None
-    row_bytes = nbytes // t.shape[0]
-    max_bytes = min(knobs.get_max_chunk_size_bytes(), _KERNEL_MAX_BYTES)
-    if row_bytes > max_bytes:
-        return None
-    rows = max_bytes // row_bytes
-    return [
-        t.narrow(0, off, min(rows, t.shape[0] - off))
-        for off in range(0, t.shape[0], rows)
-    ]
 
 
 def torch_count_nonfinite(
@@ -602,10 +614,7 @@ def build_fingerprint_items(
     kernel cannot cast to, elements that are not aligned to their size, more
     than MAX_OUTER_DIMS strided dims, or a tensor at the cap that dim 0
     cannot split."""
-    if stored_dtypes is None:
-        stored_dtypes = [None] * len(tensors)
-    if len(stored_dtypes) != len(tensors):
-        raise ValueError("stored_dtypes must have one entry per tensor")
+    stored_dtypes = _per_tensor_dtypes(stored_dtypes, len(tensors), "stored_dtypes")
     if split_bytes is None:
         split_bytes = _KERNEL_MAX_BYTES
     out: List[Optional[List[PackItem]]] = []
@@ -630,19 +639,13 @@ def build_fingerprint_items(
         if t.numel() == 0:
             out.append([])
             continue
-        stored_esz = (stored or t.dtype).itemsize
-        pieces = [t]
-        if t.numel() * stored_esz >= split_bytes:
-            row_bytes = t.numel() * stored_esz // t.shape[0] if t.dim() else 0
-            rows = split_bytes // row_bytes if row_bytes else 0
-            if rows == 0:
-                out.append(None)
-                continue
-            pieces = [
-                t.narrow(0, r, min(rows, t.shape[0] - r))
-                for r in range(0, t.shape[0], rows)
-            ]
-        if any(outer_dim_count(p) > MAX_OUTER_DIMS for p in pieces):
+        nbytes = t.numel() * (stored or t.dtype).itemsize
+        pieces: Optional[List[torch.Tensor]] = [t]
+        if nbytes >= split_bytes:
+            pieces = _split_dim0(t, nbytes, split_bytes)
+        if pieces is None or any(
+            outer_dim_count(p) > MAX_OUTER_DIMS for p in pieces
+        ):
             out.append(None)
             continue
         items, _, _ = build_pack_items(pieces, [stored] * len(pieces))
@@ -679,13 +682,12 @@ def host_fingerprint(
 
 def _items_to_flat(items: List[PackItem]) -> List[int]:
     """Serialize descriptors for the extension: fixed-width int rows."""
-    MAXD = 6
     flat: List[int] = []
     for it in items:
-        if len(it.outer_sizes) > MAXD:
+        if len(it.outer_sizes) > MAX_OUTER_DIMS:
             raise ValueError(
                 f"tensor layout too complex to pack ({len(it.outer_sizes)} "
-                "outer dims after collapsing; max 6)"
+                f"outer dims after collapsing; max {MAX_OUTER_DIMS})"
             )
         row = [
             it.src_ptr,
@@ -695,8 +697,9 @@ def _items_to_flat(items: List[PackItem]) -> List[int]:
             it.vec,
             len(it.outer_sizes),
         ]
-        sizes = list(it.outer_sizes) + [1] * (MAXD - len(it.outer_sizes))
-        strides = list(it.outer_strides) + [0] * (MAXD - len(it.outer_strides))
+        pad = MAX_OUTER_DIMS - len(it.outer_sizes)
+        sizes = list(it.outer_sizes) + [1] * pad
+        strides = list(it.outer_strides) + [0] * pad
         row += sizes + strides
         row.append(it.cast)
         flat += row
@@ -1166,42 +1169,23 @@ class StagingEngine:
         Tensors build_scan_items() declines are counted with the torch
         expression instead; so is everything when the extension is disabled
         by TSAMD_DISABLE_HIP_STAGING=1."""
-        if stored_dtypes is None:
-            stored_dtypes = [None] * len(tensors)
+        stored_dtypes = _per_tensor_dtypes(stored_dtypes, len(tensors), "stored_dtypes")
         if not self._use_ext:
             return [
                 torch_count_nonfinite(t, st)
                 for t, st in zip(tensors, stored_dtypes)
             ]
         per_tensor, classes = build_scan_items(tensors, stored_dtypes)
-        flat_items: List[PackItem] = []
-        flat_classes: List[int] = []
-        owners: List[int] = []
-        for i, (its, cls) in enumerate(zip(per_tensor, classes)):
-            for it in its or ():
-                flat_items.append(it)
-                flat_classes.append(cls)
-                owners.append(i)
-        out = [[0, 0] for _ in tensors]
-        if flat_items:
-            dev_index = self.device.index or 0
-            with torch.cuda.device(dev_index):
-                counts = _csnap.scan_nonfinite(
-                    _items_to_flat(flat_items),
-                    flat_classes,
-                    len(flat_items),
-                    torch.cuda.current_stream().cuda_stream,
-                    dev_index,
-                )
-            for k, i in enumerate(owners):
-                out[i][0] += int(counts[2 * k])
-                out[i][1] += int(counts[2 * k + 1])
-        for i, (its, cls) in enumerate(zip(per_tensor, classes)):
-            if cls is not None and its is None:
-                out[i] = list(
-                    torch_count_nonfinite(tensors[i], stored_dtypes[i])
-                )
-        return [(a, b) for a, b in out]
+        nans, infs = self._read_launch(
+            # without a class there is nothing to count: (0, 0), no fallback
+            [[] if cls is None else its for its, cls in zip(per_tensor, classes)],
+            lambda items, owners, *where: _csnap.scan_nonfinite(
+                _items_to_flat(items), [classes[i] for i in owners], len(items), *where
+            ),
+            2,
+            lambda i: torch_count_nonfinite(tensors[i], stored_dtypes[i]),
+        )
+        return list(zip(nans, infs))
 
     # -- fingerprint --------------------------------------------------------
 
@@ -1225,8 +1209,7 @@ class StagingEngine:
         instead; so is everything when the extension is disabled by
         TSAMD_DISABLE_HIP_STAGING=1. ``split_bytes`` overrides the stored
         size from which a tensor is hashed in dim-0 pieces."""
-        if stored_dtypes is None:
-            stored_dtypes = [None] * len(tensors)
+        stored_dtypes = _per_tensor_dtypes(stored_dtypes, len(tensors), "stored_dtypes")
         if not self._use_ext:
             return [
                 host_fingerprint(t, st) for t, st in zip(tensors, stored_dtypes)
@@ -1237,28 +1220,54 @@ class StagingEngine:
             t if t.is_quantized or t.layout != torch.strided else resolve_lazy(t)
             for t in tensors
         ]
-        per_tensor = build_fingerprint_items(tensors, stored_dtypes, split_bytes)
-        flat_items: List[PackItem] = []
+        (sums,) = self._read_launch(
+            build_fingerprint_items(tensors, stored_dtypes, split_bytes),
+            lambda items, owners, *where: _csnap.fingerprint_tensors(
+                _items_to_flat(items), len(items), *where
+            ),
+            1,
+            lambda i: (host_fingerprint(tensors[i], stored_dtypes[i]),),
+        )
+        return sums
+
+    # -- what the two read-only launches share -------------------------------
+
+    def _read_launch(
+        self,
+        per_tensor: Sequence[Optional[List[PackItem]]],
+        call: Callable[..., Sequence[int]],
+        words: int,
+        fallback: Callable[[int], Sequence[int]],
+    ) -> List[List[int]]:
+        """``words`` u64 results for each tensor of a batch, from ONE
+        extension call over every descriptor in ``per_tensor``; returned
+        as one list per word, each with an entry per tensor.
+        ``call(items, owners, stream, dev_index)`` makes the call and
+        returns ``words`` values per descriptor; ``owners[k]`` is the index
+        of the tensor that descriptor ``k`` belongs to. A tensor's result is
+        the sum of its descriptors' mod 2^64 (counts stay far below it),
+        zeros without descriptors. A None entry is a tensor the builder
+        declined: ``fallback(index)`` answers for it."""
+        items: List[PackItem] = []
         owners: List[int] = []
         for i, its in enumerate(per_tensor):
             for it in its or ():
-                flat_items.append(it)
+                items.append(it)
                 owners.append(i)
-        out = [0] * len(tensors)
-        if flat_items:
+        out = [[0] * len(per_tensor) for _ in range(words)]
+        if items:
             dev_index = self.device.index or 0
             with torch.cuda.device(dev_index):
-                sums = _csnap.fingerprint_tensors(
-                    _items_to_flat(flat_items),
-                    len(flat_items),
-                    torch.cuda.current_stream().cuda_stream,
-                    dev_index,
+                got = call(
+                    items, owners, torch.cuda.current_stream().cuda_stream, dev_index
                 )
-            for k, i in enumerate(owners):
-                out[i] = (out[i] + int(sums[k])) % (1 << 64)
+            for w, column in enumerate(out):
+                for i, v in zip(owners, got[w::words]):
+                    column[i] = (column[i] + v) % (1 << 64)
         for i, its in enumerate(per_tensor):
             if its is None:
-                out[i] = host_fingerprint(tensors[i], stored_dtypes[i])
+                for column, v in zip(out, fallback(i)):
+                    column[i] = v
         return out
 
     # -- debug fallback -----------------------------------------------------

@@ -16,19 +16,18 @@ exchanges the fingerprints, and every rank takes the same decision.
 from __future__ import annotations
 
 import logging
-from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
+from typing import Any, Dict, Iterable, List, Optional, Tuple
 
 import torch
 
-from . import knobs
-from .flatten import flatten
+from . import knobs, state_checks
 from .integrity import format_psum64
 from .pg_wrapper import PGWrapper
 from .stateful import AppState
 
 logger = logging.getLogger(__name__)
 
-POLICIES = ("ignore", "warn", "error")
+POLICIES = state_checks.POLICIES
 
 # {logical_path: (fingerprint hex, stored dtype, shape)} for one rank
 Finding = Tuple[str, str, Tuple[int, ...]]
@@ -54,14 +53,9 @@ def resolve_policy(replicated_check: Optional[str]) -> str:
     """The policy of one take() call: the argument, or the
     TSAMD_REPLICATED_CHECK knob when it is None. Anything else raises
     ValueError."""
-    if replicated_check is None:
-        return knobs.get_replicated_check_policy()
-    if replicated_check not in POLICIES:
-        raise ValueError(
-            f"replicated_check must be one of {'|'.join(POLICIES)} or None, "
-            f"got {replicated_check!r}"
-        )
-    return replicated_check
+    return state_checks.resolve_policy(
+        replicated_check, "replicated_check", knobs.get_replicated_check_policy
+    )
 
 
 def _local_tensor(obj: Any, dtensor_local: bool) -> Optional[torch.Tensor]:
@@ -69,14 +63,9 @@ def _local_tensor(obj: Any, dtensor_local: bool) -> Optional[torch.Tensor]:
     tensors and Parameters, and a DTensor's local shard when asked for."""
     if not isinstance(obj, torch.Tensor):
         return None
-    try:
-        from torch.distributed.tensor import DTensor
-
-        if isinstance(obj, DTensor):
-            return obj.to_local().detach() if dtensor_local else None
-    except ImportError:
-        pass
-    if type(obj) is torch.Tensor or isinstance(obj, torch.nn.Parameter):
+    if state_checks.is_dtensor(obj):
+        return obj.to_local().detach() if dtensor_local else None
+    if state_checks.is_plain_tensor(obj):
         return obj.detach()
     return None  # ShardedTensor and other subclasses
 
@@ -84,59 +73,24 @@ def _local_tensor(obj: Any, dtensor_local: bool) -> Optional[torch.Tensor]:
 def _fingerprint_leaves(
     flattened: Dict[str, Any],
     paths: Iterable[str],
-    resolve_stored: Callable[[str, Any], Optional[torch.dtype]],
+    resolve_stored: state_checks.ResolveStored,
     dtensor_local: bool,
 ) -> LocalReport:
-    from .ops import staging
-
     # unique tensors to fingerprint, and which of them each path is
-    keys: Dict[Any, int] = {}
-    tensors: List[torch.Tensor] = []
-    stored: List[Optional[torch.dtype]] = []
+    unique = state_checks.UniqueTensors()
     member: Dict[str, int] = {}
     for path in sorted(paths):
         t = _local_tensor(flattened.get(path), dtensor_local)
         if t is None or t.device.type == "meta":
             continue
-        stored_dtype = resolve_stored(path, flattened[path])
-        key: Any = len(tensors)  # sparse: no data_ptr, never aliased
-        if t.layout == torch.strided and not t.is_quantized:
-            key = (
-                t.data_ptr(),
-                t.dtype,
-                tuple(t.shape),
-                tuple(t.stride()),
-                str(t.device),
-                t.is_conj(),
-                t.is_neg(),
-                stored_dtype,
-            )
-        if key not in keys:
-            keys[key] = len(tensors)
-            tensors.append(t)
-            stored.append(stored_dtype)
-        member[path] = keys[key]
+        member[path] = unique.add(t, resolve_stored(path, flattened[path]))
 
-    sums: List[int] = [0] * len(tensors)
-    by_device: Dict[int, List[int]] = {}
-    for i, t in enumerate(tensors):
-        if t.device.type == "cuda":
-            by_device.setdefault(t.device.index or 0, []).append(i)
-        else:
-            sums[i] = staging.host_fingerprint(t, stored[i])
-    for dev_index, idxs in by_device.items():
-        engine = staging.get_staging_engine(torch.device("cuda", dev_index))
-        got = engine.fingerprint(
-            [tensors[i] for i in idxs], [stored[i] for i in idxs]
-        )
-        for i, v in zip(idxs, got):
-            sums[i] = v
-
+    sums = unique.read("host_fingerprint", "fingerprint")
     return {
         path: (
             format_psum64(sums[i]),
-            str(stored[i] or tensors[i].dtype),
-            tuple(tensors[i].shape),
+            str(unique.stored[i] or unique.tensors[i].dtype),
+            tuple(unique.tensors[i].shape),
         )
         for path, i in member.items()
     }
@@ -145,7 +99,7 @@ def _fingerprint_leaves(
 def fingerprint_leaves(
     flattened: Dict[str, Any],
     paths: Iterable[str],
-    resolve_stored: Callable[[str, Any], Optional[torch.dtype]],
+    resolve_stored: state_checks.ResolveStored,
 ) -> LocalReport:
     """``{path: (hex, stored dtype, shape)}`` for the plain tensor and
     Parameter leaves among ``paths``: the psum64 of the bytes each would be
@@ -182,13 +136,7 @@ def enforce(policy: str, local: LocalReport, pg_wrapper: PGWrapper) -> None:
     "error" raises ReplicatedStateMismatchError everywhere, "warn" logs
     once per rank."""
     rank = pg_wrapper.get_rank()
-    world_size = pg_wrapper.get_world_size()
-    gathered: List[Optional[LocalReport]] = [None] * world_size
-    if world_size > 1:
-        pg_wrapper.all_gather_object(gathered, local)
-    else:
-        gathered[0] = local
-    found = [g or {} for g in gathered]
+    found = state_checks.exchange(local, pg_wrapper)
     bad = sorted(
         path
         for path in set().union(*found)
@@ -222,17 +170,10 @@ def fingerprint_state(
     anything change since the last step?" and "do two runs agree?" without
     copying state off the device. With ``save_dtype`` (as for take) it is
     the fingerprint of what would be stored."""
-    from .snapshot import _normalize_save_dtype, _resolve_save_dtype
-
-    rules = _normalize_save_dtype(save_dtype)
-    flattened: Dict[str, Any] = {}
-    for key, stateful in app_state.items():
-        _, f = flatten(stateful.state_dict(), prefix=key)
-        flattened.update(f)
+    flattened, resolve_stored = state_checks.flatten_app_state(
+        app_state, save_dtype
+    )
     found = _fingerprint_leaves(
-        flattened,
-        flattened.keys(),
-        lambda path, obj: _resolve_save_dtype(rules, path, obj),
-        True,
+        flattened, flattened.keys(), resolve_stored, True
     )
     return {path: f[0] for path, f in found.items()}

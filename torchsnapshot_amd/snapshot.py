@@ -457,6 +457,9 @@ class Snapshot:
         if is_async:
             sources_immutable = cls._shadow_for_async(flattened)
 
+        def resolve_stored(p: str, obj: Any) -> Optional[torch.dtype]:
+            return _resolve_save_dtype(save_dtype_rules, p, obj)
+
         # non-finite policy: scan what will be staged (the hook's output,
         # the async shadow) while refusing is still free. Nothing under the
         # path has been touched yet: prepare_write and _uncommit come later,
@@ -465,10 +468,7 @@ class Snapshot:
         if nonfinite_policy != "ignore":
             _nonfinite.enforce(
                 nonfinite_policy,
-                _nonfinite.scan_leaves(
-                    flattened,
-                    lambda p, obj: _resolve_save_dtype(save_dtype_rules, p, obj),
-                ),
+                _nonfinite.scan_leaves(flattened, resolve_stored),
                 pg_wrapper,
             )
 
@@ -481,9 +481,7 @@ class Snapshot:
             _replication.enforce(
                 replicated_policy,
                 _replication.fingerprint_leaves(
-                    flattened,
-                    replicated_paths,
-                    lambda p, obj: _resolve_save_dtype(save_dtype_rules, p, obj),
+                    flattened, replicated_paths, resolve_stored
                 ),
                 pg_wrapper,
             )
