@@ -14,6 +14,7 @@ from .rng_state import RNGState
 from .snapshot import PendingSnapshot, Snapshot
 from .state_dict import StateDict
 from .stateful import AppState, Stateful
+from .tensor_stats import TensorStats, tensor_stats
 from .version import __version__
 
 __all__ = [
@@ -27,5 +28,7 @@ __all__ = [
     "find_nonfinite",
     "ReplicatedStateMismatchError",
     "fingerprint_state",
+    "TensorStats",
+    "tensor_stats",
     "__version__",
 ]

@@ -2,6 +2,8 @@
 
     python -m torchsnapshot_amd inspect <path>       # manifest tree + sizes
     python -m torchsnapshot_amd cat <path> <entry>   # print one object
+    python -m torchsnapshot_amd stats <path> [--against <other>]
+                                                     # recorded statistics
 """
 
 from __future__ import annotations
@@ -87,6 +89,43 @@ def cmd_cat(args: argparse.Namespace) -> int:
     return 0
 
 
+def _fmt(x) -> str:
+    return "-" if x is None else f"{x:.6g}"
+
+
+def cmd_stats(args: argparse.Namespace) -> int:
+    from .tensor_stats import relative_change
+
+    stats = Snapshot(args.path).get_stats()
+    if not stats:
+        print(f"{args.path}: no statistics recorded (take(..., stats=True))")
+        return 1
+    against = None
+    if args.against is not None:
+        against = Snapshot(args.against).get_stats()
+    rows = []
+    for path, s in stats.items():
+        line = (
+            f"{path}: n_finite={s.n_finite} n_zero={s.n_zero} "
+            f"min={_fmt(s.min)} max={_fmt(s.max)} mean={_fmt(s.mean)} "
+            f"rms={_fmt(s.rms)} absmax={_fmt(s.absmax)}"
+        )
+        change = -1.0
+        if against is not None:
+            old = against.get(path)
+            d_rms = relative_change(s.rms, old.rms) if old else None
+            d_abs = relative_change(s.absmax, old.absmax) if old else None
+            line += f" d_rms={_fmt(d_rms)} d_absmax={_fmt(d_abs)}"
+            change = max((d for d in (d_rms, d_abs) if d is not None), default=-1.0)
+        rows.append((change, line))
+    if against is not None:
+        # the leaves that moved most first
+        rows.sort(key=lambda r: -r[0])
+    for _, line in rows:
+        print(line)
+    return 0
+
+
 def main(argv=None) -> int:
     parser = argparse.ArgumentParser(prog="python -m torchsnapshot_amd")
     sub = parser.add_subparsers(dest="cmd", required=True)
@@ -98,6 +137,17 @@ def main(argv=None) -> int:
     p_cat.add_argument("path")
     p_cat.add_argument("entry")
     p_cat.set_defaults(fn=cmd_cat)
+    p_stats = sub.add_parser(
+        "stats", help="print the statistics recorded by take(..., stats=True)"
+    )
+    p_stats.add_argument("path")
+    p_stats.add_argument(
+        "--against",
+        metavar="OTHER",
+        help="also print the relative change of rms and absmax since the "
+        "snapshot at OTHER, largest first",
+    )
+    p_stats.set_defaults(fn=cmd_stats)
     args = parser.parse_args(argv)
     return args.fn(args)
 

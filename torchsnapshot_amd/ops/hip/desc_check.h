@@ -8,8 +8,8 @@
 // wu_prefix_of, grid_for, LaunchTables).
 //
 // Every entry point of the extension that takes descriptor rows -
-// pack_d2h, scatter_h2d, unpack_h2d, scan_nonfinite, fingerprint_tensors -
-// runs check_descs before it touches the GPU: a row that would make a
+// pack_d2h, scatter_h2d, unpack_h2d, scan_nonfinite, fingerprint_tensors,
+// tensor_stats - runs check_descs before it touches the GPU: a row that would make a
 // kernel issue a misaligned vector access, index past its rows, or wrap a
 // u32 index is a std::runtime_error here, not a device fault there.
 
@@ -71,6 +71,8 @@ constexpr uint32_t kScanFNUZ = 6;  // e4m3fnuz and e5m2fnuz: NaN is 0x80
 constexpr uint32_t kScanF32asF16 = 7;
 constexpr uint32_t kScanF32asBF16 = 8;
 constexpr uint32_t kScanClasses = 9;
+// tensor_stats takes the first four: the classes that widen exactly to f64
+constexpr uint32_t kStatsClasses = kScanBF16 + 1;
 
 constexpr uint32_t scan_elem_size(uint32_t cls) {
   return cls == kScanF64 ? 8u
@@ -127,6 +129,8 @@ enum class DescKind {
   Scan,     // scan_nonfinite: no cast code; needs one class per descriptor
   Fingerprint,  // fingerprint_tensors: cast codes 0..2; flat_off is a hash
                 // offset and must be a multiple of vec
+  Stats,    // tensor_stats: no cast code; one class per descriptor, below
+            // kStatsClasses
 };
 
 // unpack_h2d's flat side: where the payload sits and how long it is
@@ -156,6 +160,7 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
                           : kind == DescKind::Scatter ? "scatter_h2d: "
                           : kind == DescKind::Unpack  ? "unpack_h2d: "
                           : kind == DescKind::Scan    ? "scan_nonfinite: "
+                          : kind == DescKind::Stats   ? "tensor_stats: "
                                                       : "fingerprint_tensors: ";
   auto refuse = [&who](const char* what) {
     throw std::runtime_error(who + what);
@@ -165,8 +170,8 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
     if (flat->hash_byte0 % 8 != 0) refuse("hash_byte0 must be 8-aligned");
     if (flat->slab_ptr % 16 != 0) refuse("slab must be 16-aligned");
   }
-  if (kind == DescKind::Scan &&
-      (classes == nullptr || classes->size() != descs.size())) {
+  const bool classed = kind == DescKind::Scan || kind == DescKind::Stats;
+  if (classed && (classes == nullptr || classes->size() != descs.size())) {
     refuse("one class code per descriptor");
   }
   for (size_t i = 0; i < descs.size(); ++i) {
@@ -196,6 +201,10 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
           refuse("widening cast descriptors are scatter-only (unpack_h2d)");
         }
         break;
+      case DescKind::Stats:
+        if ((*classes)[i] >= kStatsClasses) refuse("unknown element class");
+        if (cast) refuse("cast descriptors not allowed");
+        break;
     }
     if (d.nbytes == 0) continue;
     if (d.nbytes > kMaxDescBytes) {
@@ -211,7 +220,7 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
       refuse(cast ? "cast descriptor: vec must be 16/8/4/2"
                   : "vec must be 16/8/4/2/1");
     }
-    if (kind == DescKind::Scan && v < scan_elem_size((*classes)[i])) {
+    if (classed && v < scan_elem_size((*classes)[i])) {
       refuse("vec below the element size");
     }
     if (d.row_bytes == 0 || d.row_bytes % v != 0 ||
@@ -228,8 +237,8 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
     }
     // the widest single access on the tensor side
     const unsigned long long align = !cast ? v : v == 16 ? 16 : 2ull * v;
-    // the two kinds whose kernels only load
-    const bool reads = kind == DescKind::Scan || kind == DescKind::Fingerprint;
+    // the kinds whose kernels only load
+    const bool reads = classed || kind == DescKind::Fingerprint;
     bool ok = reinterpret_cast<uintptr_t>(d.tensor_base) % align == 0;
     unsigned long long rows = 1;
     for (uint32_t k = 0; k < d.ndim; ++k) {

@@ -15,6 +15,9 @@
 //     read-only, one launch for the whole state (the nonfinite= policy)
 //   - fingerprint kernel: the psum64 of each tensor's stored bytes, read in
 //     place over the same descriptors (the replicated_check= policy)
+//   - stats kernel: count, zeros, min, max, sum and sum of squares of each
+//     tensor's finite elements in f64, read in place over the same
+//     descriptors, with sums that are bit-identical for any grid (stats=)
 //   - SDMA copies (hipMemcpyAsync) slab <-> pinned host memory; the slab
 //     can also be skipped entirely ("direct" mode): the kernel writes
 //     gathered bytes straight into pinned host memory over PCIe
@@ -36,8 +39,8 @@
 //   - on the host (desc_check.h): parse_descs + check_descs validate every
 //     descriptor before the GPU is touched; wu_prefix_of, grid_for and
 //     LaunchTables are the launch prologue of both launchers: launch_pack
-//     for the copies, read_launch for the blocking read-only scan and
-//     fingerprint
+//     for the copies, read_launch for the blocking read-only scan,
+//     fingerprint and statistics
 //   - on the host (table_ring.h): the launch tables reach the device
 //     through a ring of pinned slots, so a launch never waits for the
 //     stream it enqueues on, and the launch entry points hold no GIL
@@ -69,6 +72,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -909,6 +913,299 @@ __global__ __launch_bounds__(kBlockThreads) void fingerprint_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// tensor statistics: six u64 words per descriptor over its FINITE elements
+// (NaN and +-Inf are skipped; counting them is the scan's job), read in
+// place and read-only like the scan, with the scan's descriptors (no flat
+// side, one class per descriptor beside them: f64, f32, f16, bf16):
+//
+//   0  n_finite                      4  sum, f64 bits
+//   1  n_zero (+0 and -0)            5  sum of squares, f64 bits
+//   2  minimum, as a key             (key = order-preserving u64 image of
+//   3  maximum, as a key              the value widened to f64)
+//
+//   - widening: every class widens to f64 exactly. It is done on the bit
+//     patterns (f16 -> f32 with the restore's f16_to_f32_bits, bf16 by a
+//     shift, f32 -> f64 below), so f16, bf16 and f32 subnormals come out
+//     exact whatever the wave's f32 denormal mode is. The f64 additions and
+//     the multiply are written as __dadd_rn / __dmul_rn: never contracted
+//     into an fma, so what a lane computes does not depend on how the
+//     compiler schedules an instantiation. Only an f64 tensor can produce an
+//     f64 subnormal operand (the square of the smallest f32 subnormal is
+//     2^-298), and f64 denormals are kept by the kernel's float mode
+//   - key: bits ^ (sign ? ~0 : 1 << 63). Keys compare as unsigned integers
+//     the way the values compare as numbers (-0 below +0). No finite value
+//     has the key 0 or ~0 (both are NaN patterns), so the launcher's initial
+//     words, ~0 for the minimum and 0 for the maximum, mean "no finite
+//     element" and never win against a real key
+//   - words 0-3: lane registers, carried from one work unit to the next
+//     while the workgroup stays on one descriptor, as the fingerprint
+//     carries its sum. When it moves on: add_per_wave for the counters, a
+//     wave64 shuffle min / max and ONE atomicMin / atomicMax per wave for
+//     the keys. Integer min, max and addition are associative and
+//     commutative: any grid and any order give the same words
+//   - words 4-5 are floating-point sums, and f64 addition is not
+//     associative: a float atomic, or carrying, would make the result
+//     depend on the grid size and on which workgroup lands first, and ranks
+//     compare and merge these values. So they are reduced in two stages of
+//     fixed shape. Stage one, per 64 KiB work unit: a lane adds its elements
+//     in traversal order (a function of the descriptor, the unit and the
+//     lane alone); a fixed wave64 shuffle tree follows; the four wave
+//     results go through LDS and thread 0 adds them in wave order and stores
+//     the pair at partials[2 * global work-unit number]. Stage two,
+//     stats_finish_kernel, one wave per descriptor on the same stream: lane
+//     l adds partials l, l + 64, ... of the descriptor's work units in that
+//     order, then the same tree. The grid size, the order of workgroups and
+//     the descriptor's place in the batch do not enter anywhere
+//   - LDS: 64 bytes (4 waves x 2 doubles). It is the first use of LDS among
+//     these kernels because it is the first reduction here that has to
+//     cross waves in a FIXED order; everything else reduces with atomics,
+//     whose order is free because integer addition does not care
+//   - loads: the widest the descriptor allows, UNROLL 4 on the contiguous
+//     loop like the scan; every element of a loaded word is classified
+//     and accumulated without a branch (a non-finite element contributes
+//     0.0 to the sums and the neutral key to min and max)
+// ---------------------------------------------------------------------------
+
+// finite f32 pattern -> the f64 pattern of the same value
+__device__ __host__ inline unsigned long long f32_to_f64_bits(uint32_t u) {
+  const unsigned long long sign = (unsigned long long)(u & 0x80000000u) << 32;
+  const uint32_t exp = (u >> 23) & 0xFFu;
+  const uint32_t mant = u & 0x007FFFFFu;
+  if (exp != 0u) {
+    // rebias 127 -> 1023; 23 mantissa bits move to the top of 52
+    return sign | ((unsigned long long)(exp + 896u) << 52) |
+           ((unsigned long long)mant << 29);
+  }
+  if (mant == 0u) return sign;  // +-0
+  // subnormal: mant * 2^-149. Shift the leading one up to bit 23 (the
+  // implicit bit); each position shifted lowers the exponent from 2^-126
+  const uint32_t shift = (uint32_t)__builtin_clz(mant) - 8u;  // 1..23
+  return sign | ((unsigned long long)(897u - shift) << 52) |
+         ((unsigned long long)((mant << shift) & 0x007FFFFFu) << 29);
+}
+
+// What one lane keeps. The counters, like the scan's, fit u32 within a work
+// unit; the kernel adds them into u64 ones it carries.
+struct StatsLane {
+  uint32_t n_finite = 0, n_zero = 0;
+  unsigned long long kmin = ~0ull, kmax = 0ull;
+  double sum = 0.0, sumsq = 0.0;
+};
+
+// one element, given as an f64 pattern and whether it is finite
+__device__ __forceinline__ void stats_elem(unsigned long long b, bool finite,
+                                           StatsLane& a) {
+  const unsigned long long key =
+      b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull);
+  const unsigned long long klo = finite ? key : ~0ull;
+  const unsigned long long khi = finite ? key : 0ull;
+  a.kmin = klo < a.kmin ? klo : a.kmin;
+  a.kmax = khi > a.kmax ? khi : a.kmax;
+  a.n_finite += finite;
+  a.n_zero += finite & ((b << 1) == 0ull);  // +0 and -0
+  const double x = finite ? __longlong_as_double((long long)b) : 0.0;
+  a.sum = __dadd_rn(a.sum, x);
+  a.sumsq = __dadd_rn(a.sumsq, __dmul_rn(x, x));
+}
+
+__device__ __forceinline__ void stats_f32(uint32_t u, StatsLane& a) {
+  const bool finite = (u & 0x7FFFFFFFu) < 0x7F800000u;
+  // the widening of a non-finite pattern is some pattern nobody looks at
+  stats_elem(f32_to_f64_bits(u), finite, a);
+}
+
+__device__ __forceinline__ void stats_f64(uint32_t lo, uint32_t hi,
+                                          StatsLane& a) {
+  const unsigned long long b = ((unsigned long long)hi << 32) | lo;
+  const bool finite = (b & 0x7FFFFFFFFFFFFFFFull) < 0x7FF0000000000000ull;
+  stats_elem(b, finite, a);
+}
+
+// the elements of one loaded 32-bit word (one for f32, two for f16 / bf16)
+template <uint32_t CLS>
+__device__ __forceinline__ void stats_word(uint32_t w, StatsLane& a) {
+  if (CLS == kScanF32) {
+    stats_f32(w, a);
+  } else if (CLS == kScanBF16) {
+    stats_f32(w << 16, a);
+    stats_f32(w & 0xFFFF0000u, a);
+  } else {  // kScanF16; inf and NaN stay inf and NaN in f32
+    stats_f32(f16_to_f32_bits(w & 0xFFFFu), a);
+    stats_f32(f16_to_f32_bits(w >> 16), a);
+  }
+}
+
+// One naturally aligned VEC-byte load (VEC >= the element size) and every
+// element in it. Unlike the scan, a zero element counts here, so the one
+// load that is narrower than a word (a single 16-bit element) is not
+// padded.
+template <int VEC, uint32_t CLS>
+__device__ __forceinline__ void stats_vec(const char* p, StatsLane& a) {
+  if (VEC == 16) {
+    const uint4 v = *reinterpret_cast<const uint4*>(p);
+    if (CLS == kScanF64) {
+      stats_f64(v.x, v.y, a);
+      stats_f64(v.z, v.w, a);
+    } else {
+      stats_word<CLS>(v.x, a);
+      stats_word<CLS>(v.y, a);
+      stats_word<CLS>(v.z, a);
+      stats_word<CLS>(v.w, a);
+    }
+  } else if (VEC == 8) {
+    const uint2 v = *reinterpret_cast<const uint2*>(p);
+    if (CLS == kScanF64) {
+      stats_f64(v.x, v.y, a);
+    } else {
+      stats_word<CLS>(v.x, a);
+      stats_word<CLS>(v.y, a);
+    }
+  } else if (VEC == 4) {
+    if (CLS != kScanF64) stats_word<CLS>(*reinterpret_cast<const uint32_t*>(p), a);
+  } else if (VEC == 2) {
+    const uint32_t h = *reinterpret_cast<const uint16_t*>(p);
+    if (CLS == kScanBF16) stats_f32(h << 16, a);
+    else if (CLS == kScanF16) stats_f32(f16_to_f32_bits(h), a);
+  }
+}
+
+// The class switch sits outside the traversal, as in scan_class; the host
+// refuses vec below the element size, so those pairs are not instantiated.
+template <uint32_t CLS>
+__device__ __forceinline__ void stats_class(const Desc& d, uint32_t s,
+                                            uint32_t e, StatsLane& a) {
+  constexpr uint32_t ESZ = scan_elem_size(CLS);
+  auto range = [&](auto vec) {
+    constexpr int VEC = decltype(vec)::value;
+    for_each_vec<VEC, 1, 4>(d, s, e, [&](unsigned long long, const char* p) {
+      stats_vec<VEC, CLS>(p, a);
+    });
+  };
+  switch (d.vec) {
+    case 16: range(std::integral_constant<int, 16>{}); break;
+    case 8: range(std::integral_constant<int, 8>{}); break;
+    case 4:
+      if constexpr (ESZ <= 4) range(std::integral_constant<int, 4>{});
+      break;
+    default:
+      if constexpr (ESZ <= 2) range(std::integral_constant<int, 2>{});
+      break;
+  }
+}
+
+// the fixed wave64 tree of the two-stage sums: lane 0 ends with the result
+__device__ __forceinline__ double wave_sum_fixed(double v) {
+  for (int delta = 32; delta > 0; delta >>= 1) {
+    v = __dadd_rn(v, __shfl_down(v, delta, 64));
+  }
+  return v;
+}
+
+// wave64 min / max of the keys and one atomic per wave; none for a wave
+// that saw no finite element
+__device__ __forceinline__ void minmax_per_wave(unsigned long long* out,
+                                                unsigned long long kmin,
+                                                unsigned long long kmax) {
+  for (int delta = 32; delta > 0; delta >>= 1) {
+    const unsigned long long lo = __shfl_down(kmin, delta, 64);
+    const unsigned long long hi = __shfl_down(kmax, delta, 64);
+    kmin = lo < kmin ? lo : kmin;
+    kmax = hi > kmax ? hi : kmax;
+  }
+  if ((threadIdx.x & 63) == 0 && kmax != 0ull) {
+    atomicMin(&out[2], kmin);
+    atomicMax(&out[3], kmax);
+  }
+}
+
+// out[6*i ..]: the six words of descriptor i; the launcher sets word 2 to
+// ~0 and the rest to zero. Words 4-5 are left to stats_finish_kernel;
+// partials[2*wu], partials[2*wu + 1]: sum and sum of squares of work unit
+// wu, every one of which is written exactly once.
+__global__ __launch_bounds__(kBlockThreads) void stats_kernel(
+    const Desc* __restrict__ descs, const uint32_t* __restrict__ classes,
+    int n, const unsigned long long* __restrict__ wu_prefix,
+    unsigned long long total_wus, unsigned long long* __restrict__ out,
+    double* __restrict__ partials) {
+  __shared__ double wave_sums[kBlockThreads / 64][2];
+  unsigned long long n_finite = 0, n_zero = 0;
+  unsigned long long kmin = ~0ull, kmax = 0ull;
+  int cur = -1;
+  auto flush = [&]() {
+    add_per_wave(&out[6 * cur], n_finite);
+    add_per_wave(&out[6 * cur + 1], n_zero);
+    minmax_per_wave(&out[6 * cur], kmin, kmax);
+  };
+  for_each_work_unit(
+      descs, n, wu_prefix, total_wus,
+      [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
+        if (owner != cur) {
+          if (cur >= 0) flush();
+          n_finite = n_zero = 0;
+          kmin = ~0ull;
+          kmax = 0ull;
+          cur = owner;
+        }
+        StatsLane a;
+        a.kmin = kmin;
+        a.kmax = kmax;
+        switch (classes[owner]) {
+          case kScanF64: stats_class<kScanF64>(d, s, e, a); break;
+          case kScanF32: stats_class<kScanF32>(d, s, e, a); break;
+          case kScanF16: stats_class<kScanF16>(d, s, e, a); break;
+          default: stats_class<kScanBF16>(d, s, e, a); break;
+        }
+        n_finite += a.n_finite;
+        n_zero += a.n_zero;
+        kmin = a.kmin;
+        kmax = a.kmax;
+        // stage one of the sums. The owner, and so the path to here, is
+        // uniform across the workgroup: every thread reaches both barriers
+        const double ws = wave_sum_fixed(a.sum);
+        const double wq = wave_sum_fixed(a.sumsq);
+        if ((threadIdx.x & 63) == 0) {
+          wave_sums[threadIdx.x >> 6][0] = ws;
+          wave_sums[threadIdx.x >> 6][1] = wq;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+          double us = wave_sums[0][0], uq = wave_sums[0][1];
+          for (int w = 1; w < kBlockThreads / 64; ++w) {
+            us = __dadd_rn(us, wave_sums[w][0]);
+            uq = __dadd_rn(uq, wave_sums[w][1]);
+          }
+          const unsigned long long wu = wu_prefix[owner] + s / kWorkUnitBytes;
+          partials[2 * wu] = us;
+          partials[2 * wu + 1] = uq;
+        }
+        __syncthreads();  // before the next unit's waves overwrite the LDS
+      });
+  if (cur >= 0) flush();
+}
+
+// Stage two: one wave per descriptor. Lane l adds partials l, l + 64, ...
+// of the descriptor's work units in that order, the fixed tree follows, and
+// lane 0 stores words 4 and 5.
+__global__ __launch_bounds__(64) void stats_finish_kernel(
+    int n, const unsigned long long* __restrict__ wu_prefix,
+    const double* __restrict__ partials, unsigned long long* __restrict__ out) {
+  const int i = blockIdx.x;
+  if (i >= n) return;
+  const unsigned long long end = wu_prefix[i + 1];
+  double s = 0.0, q = 0.0;
+  for (unsigned long long wu = wu_prefix[i] + threadIdx.x; wu < end; wu += 64) {
+    s = __dadd_rn(s, partials[2 * wu]);
+    q = __dadd_rn(q, partials[2 * wu + 1]);
+  }
+  s = wave_sum_fixed(s);
+  q = wave_sum_fixed(q);
+  if (threadIdx.x == 0) {
+    out[6 * i + 4] = (unsigned long long)__double_as_longlong(s);
+    out[6 * i + 5] = (unsigned long long)__double_as_longlong(q);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host-side op management
 // ---------------------------------------------------------------------------
 
@@ -1188,14 +1485,18 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
 // GPU work. Runs on the D2H side stream, after the producer's. One device
 // allocation holds `tables` and `n_results` zeroed u64 behind them;
 // `launch(d_tables, d_results, stream)` enqueues the kernel. A HIP error
-// is thrown with `what` in front.
+// is thrown with `what` in front. With `init` (n_results words) the results
+// start from those values and not from zero; `scratch_bytes` more bytes of
+// the same allocation, uninitialised, follow the results at
+// d_results + n_results and never come back to the host.
 template <typename Launch>
-std::vector<unsigned long long> read_launch(const LaunchTables& tables,
-                                            size_t n_results,
-                                            uintptr_t producer_stream,
-                                            int device, const char* what,
-                                            Launch launch) {
-  std::vector<unsigned long long> results(n_results, 0);
+std::vector<unsigned long long> read_launch(
+    const LaunchTables& tables, size_t n_results, uintptr_t producer_stream,
+    int device, const char* what, Launch launch,
+    const std::vector<unsigned long long>* init = nullptr,
+    size_t scratch_bytes = 0) {
+  std::vector<unsigned long long> results =
+      init != nullptr ? *init : std::vector<unsigned long long>(n_results, 0);
   const size_t table_bytes = tables.host.size();
   const size_t result_bytes = sizeof(unsigned long long) * n_results;
 
@@ -1206,14 +1507,19 @@ std::vector<unsigned long long> read_launch(const LaunchTables& tables,
   chain_after(stream, producer_stream, device);
 
   void* scratch = nullptr;
-  HIP_CHECK(hipMallocAsync(&scratch, table_bytes + result_bytes, stream));
+  HIP_CHECK(hipMallocAsync(&scratch,
+                           table_bytes + result_bytes + scratch_bytes, stream));
   unsigned long long* d_results = reinterpret_cast<unsigned long long*>(
       static_cast<char*>(scratch) + table_bytes);
 
   // enqueue everything, then synchronise whatever happened: the host
   // buffers (`tables`, `results`) must outlive the copies that read and
   // write them
-  hipError_t err = hipMemsetAsync(d_results, 0, result_bytes, stream);
+  hipError_t err =
+      init != nullptr
+          ? hipMemcpyAsync(d_results, results.data(), result_bytes,
+                           hipMemcpyHostToDevice, stream)
+          : hipMemsetAsync(d_results, 0, result_bytes, stream);
   if (err == hipSuccess) {
     err = hipMemcpyAsync(scratch, tables.host.data(), table_bytes,
                          hipMemcpyHostToDevice, stream);
@@ -1464,6 +1770,68 @@ static std::vector<unsigned long long> fingerprint_tensors(
       });
 }
 
+// ---------------------------------------------------------------------------
+// value statistics of N strided device tensors (blocking): one launch of
+// stats_kernel and one of stats_finish_kernel. `flat` holds scan-style
+// descriptor rows (cast 0, flat_off ignored), `classes` one of the first
+// four kScan* codes per descriptor. Returns 6*n words (see stats_kernel);
+// a descriptor without finite elements keeps 0, 0, ~0, 0, +0.0, +0.0.
+// `max_grid` > 0 bounds the workgroups of the first kernel below the cap: a
+// save beside heavy training may want fewer CUs taken, and no word depends
+// on it.
+// ---------------------------------------------------------------------------
+
+static std::vector<unsigned long long> tensor_stats(
+    const std::vector<unsigned long long>& flat, int n,
+    const std::vector<uint32_t>& classes, int device,
+    uintptr_t producer_stream, unsigned int max_grid) {
+  // refused before the GPU is touched, under the scan's rules
+  const std::vector<Desc> descs = parse_descs(flat, n);
+  check_descs(descs, DescKind::Stats, nullptr, &classes);
+
+  std::vector<unsigned long long> init(6 * (size_t)n, 0);
+  for (size_t i = 0; i < (size_t)n; ++i) init[6 * i + 2] = ~0ull;
+
+  const std::vector<unsigned long long> wu_prefix = wu_prefix_of(descs);
+  const unsigned long long total_wus = wu_prefix[n];
+  if (total_wus == 0) return init;
+
+  // descriptors | prefix sums | classes
+  const LaunchTables tables(descs, wu_prefix, classes.data(),
+                            sizeof(uint32_t) * n);
+
+  // An HBM read with f64 work behind every element. 2048 workgroups put
+  // eight on each of the 256 CUs, and keep a workgroup on one large tensor
+  // for many work units, so that words 0-3 are carried and cost one round
+  // of atomics per tensor, not one per unit. TSAMD_PACK_GRID replaces the
+  // cap only when the caller names no bound of its own.
+  constexpr unsigned long long kStatsGridCap = 2048;
+  const unsigned int grid =
+      max_grid > 0
+          ? grid_for(total_wus,
+                     max_grid < kStatsGridCap ? max_grid : kStatsGridCap,
+                     nullptr)
+          : grid_for(total_wus, kStatsGridCap, getenv("TSAMD_PACK_GRID"));
+
+  return read_launch(
+      tables, init.size(), producer_stream, device, "tensor_stats: ",
+      [&](const void* d_tables, unsigned long long* d_out,
+          hipStream_t stream) {
+        // the partial sums of stage one: two doubles per work unit, behind
+        // the results in the same allocation
+        double* d_partials = reinterpret_cast<double*>(d_out + init.size());
+        hipLaunchKernelGGL(
+            stats_kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
+            tables.descs(d_tables),
+            static_cast<const uint32_t*>(tables.extra(d_tables)), n,
+            tables.prefix(d_tables), total_wus, d_out, d_partials);
+        hipLaunchKernelGGL(stats_finish_kernel, dim3((unsigned int)n),
+                           dim3(64), 0, stream, n, tables.prefix(d_tables),
+                           static_cast<const double*>(d_partials), d_out);
+      },
+      &init, (size_t)total_wus * 2 * sizeof(double));
+}
+
 // Host-side psum64 (single pass, std::thread-parallel): the
 // python-level vectorized implementations burn ~10 full memory passes
 // on splitmix temporaries (~0.2-0.3 GB/s); this one runs at memcpy-ish
@@ -1678,6 +2046,13 @@ PYBIND11_MODULE(_csnap, m) {
         "offset flat_off",
         py::arg("flat"), py::arg("n"), py::arg("producer_stream"),
         py::arg("device"));
+  m.def("tensor_stats", &tensor_stats,
+        "value statistics of strided device tensors over their finite "
+        "elements, read in place (blocking); six words per descriptor: "
+        "n_finite, n_zero, min key, max key, sum and sum of squares as f64 "
+        "bits; max_grid > 0 bounds the workgroups",
+        py::arg("flat"), py::arg("n"), py::arg("classes"), py::arg("device"),
+        py::arg("stream"), py::arg("max_grid") = 0);
   m.def("file_write", &::file_write,  // not tsamd::file_write
        
         "write a buffer to a file (GIL released); reuse=True overwrites an "

@@ -25,9 +25,10 @@ from __future__ import annotations
 
 import contextlib
 import math
+import struct
 import threading
 from dataclasses import dataclass
-from typing import Callable, Dict, Iterator, List, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, Iterator, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -680,6 +681,148 @@ def host_fingerprint(
     return psum64_value(flat.numpy())
 
 
+# ---------------------------------------------------------------------------
+# tensor statistics: descriptors, the six words, host fallbacks
+# ---------------------------------------------------------------------------
+
+# Six u64 words per tensor, over its finite elements (stats_kernel in
+# ops/hip/staging.hip): n_finite, n_zero, minimum and maximum as keys, sum
+# and sum of squares as float64 bit patterns. The classes are the first four
+# of the scan's: the dtypes that widen to float64 exactly.
+_STATS_CLASSES = {
+    dt: cls for dt, cls in _SCAN_CLASSES.items() if cls <= SCAN_BF16
+}
+_M64 = (1 << 64) - 1
+# no finite element: the minimum key all ones, the maximum key zero
+STATS_EMPTY = (0, 0, _M64, 0, 0, 0)
+
+
+def stats_key(x: float) -> int:
+    """Order-preserving u64 image of a finite float64: keys compare as
+    unsigned integers the way the values compare (-0.0 below +0.0)."""
+    (b,) = struct.unpack("<Q", struct.pack("<d", x))
+    return b ^ (_M64 if b >> 63 else 1 << 63)
+
+
+def stats_unkey(key: int) -> float:
+    b = key ^ (1 << 63 if key >> 63 else _M64)
+    return struct.unpack("<d", struct.pack("<Q", b))[0]
+
+
+def _f64_bits(x: float) -> int:
+    return struct.unpack("<Q", struct.pack("<d", x))[0]
+
+
+def _f64_of(bits: int) -> float:
+    return struct.unpack("<d", struct.pack("<Q", bits))[0]
+
+
+def merge_stats(a: Sequence[int], b: Sequence[int]) -> List[int]:
+    """The six words of two disjoint sets of elements taken together: counts
+    add, keys take min / max, the sums add as float64, ``a`` first."""
+    return [
+        a[0] + b[0],
+        a[1] + b[1],
+        min(a[2], b[2]),
+        max(a[3], b[3]),
+        _f64_bits(_f64_of(a[4]) + _f64_of(b[4])),
+        _f64_bits(_f64_of(a[5]) + _f64_of(b[5])),
+    ]
+
+
+def decode_stats(words: Sequence[int]) -> Dict[str, Any]:
+    """``{n_finite, n_zero, min, max, sum, sumsq}`` of six words; ``min``
+    and ``max`` are None when there is no finite element."""
+    some = words[0] > 0
+    return {
+        "n_finite": words[0],
+        "n_zero": words[1],
+        "min": stats_unkey(words[2]) if some else None,
+        "max": stats_unkey(words[3]) if some else None,
+        "sum": _f64_of(words[4]),
+        "sumsq": _f64_of(words[5]),
+    }
+
+
+def _stats_view(t: torch.Tensor) -> Optional[torch.Tensor]:
+    """The tensor whose elements the statistics are of, or None when it
+    gets none: fp8, complex, integer, quantized and sparse tensors."""
+    if t.is_quantized or t.layout != torch.strided:
+        return None
+    return t.detach() if t.dtype in _STATS_CLASSES else None
+
+
+def build_stats_items(
+    tensors: Sequence[torch.Tensor],
+) -> Tuple[List[Optional[List[PackItem]]], List[Optional[int]]]:
+    """Stats-kernel descriptors for a batch, one entry per tensor: the
+    scan's descriptors (collapsed in stride order, since no statistic
+    depends on element order) under build_scan_items' conventions.
+    ``classes[i]`` is None for a tensor that gets no statistics;
+    ``items[i]`` is ``[]`` without elements, several descriptors for a
+    tensor over the kernel's size cap (their words merge), and None when
+    the builder declines and the caller computes with torch: a lazy
+    negative view, more than 6 outer dims after collapsing, a storage
+    offset that splits an element, or a tensor that dim 0 cannot split."""
+    items: List[Optional[List[PackItem]]] = []
+    classes: List[Optional[int]] = []
+    for t in tensors:
+        view = _stats_view(t)
+        classes.append(None if view is None else _STATS_CLASSES[view.dtype])
+        if view is None:
+            items.append(None)
+            continue
+        nbytes = view.numel() * view.element_size()
+        if nbytes == 0:
+            items.append([])
+            continue
+        pieces: Optional[List[torch.Tensor]] = [view]
+        if nbytes > _KERNEL_MAX_BYTES:
+            pieces = _split_dim0(
+                view,
+                nbytes,
+                min(knobs.get_max_chunk_size_bytes(), _KERNEL_MAX_BYTES),
+            )
+        built = None if pieces is None else [_build_scan_item(p) for p in pieces]
+        if built is None or any(it is None for it in built):
+            items.append(None)
+        else:
+            items.append(built)
+    return items, classes
+
+
+def torch_tensor_stats(
+    t: torch.Tensor, stored_dtype: Optional[torch.dtype] = None
+) -> List[int]:
+    """The six words by torch expressions in float64, on the tensor's own
+    device: what the stats kernel must agree with (exactly in the counts,
+    minimum and maximum; to rounding in the sums), and the path for
+    anything it declines. STATS_EMPTY for a tensor that gets no statistics.
+    ``stored_dtype`` is ignored: statistics are of the live values."""
+    view = _stats_view(t)
+    if view is None:
+        return list(STATS_EMPTY)
+    x = resolve_lazy(view).to(torch.float64).reshape(-1)
+    x = x[torch.isfinite(x)]
+    if x.numel() == 0:
+        return list(STATS_EMPTY)
+    return [
+        x.numel(),
+        int((x == 0).sum()),
+        stats_key(float(x.min())),
+        stats_key(float(x.max())),
+        _f64_bits(float(x.sum())),
+        _f64_bits(float((x * x).sum())),
+    ]
+
+
+def host_tensor_stats(
+    t: torch.Tensor, stored_dtype: Optional[torch.dtype] = None
+) -> List[int]:
+    """torch_tensor_stats() on the host: the path for host tensors."""
+    return torch_tensor_stats(t.detach().cpu(), stored_dtype)
+
+
 def _items_to_flat(items: List[PackItem]) -> List[int]:
     """Serialize descriptors for the extension: fixed-width int rows."""
     flat: List[int] = []
@@ -1230,7 +1373,52 @@ class StagingEngine:
         )
         return sums
 
-    # -- what the two read-only launches share -------------------------------
+    # -- tensor statistics --------------------------------------------------
+
+    def stats(
+        self,
+        tensors: Sequence[torch.Tensor],
+        stored_dtypes: Optional[Sequence[Optional[torch.dtype]]] = None,
+        max_grid: int = 0,
+    ) -> List[List[int]]:
+        """The six statistics words (decode_stats) of each of this device's
+        ``tensors`` over its finite elements, from ONE read-only launch of
+        the stats kernel over all of them. Blocking.
+
+        Counts, minimum and maximum are exact. The sums are float64 and
+        deterministic: the same tensor gives the same bits whatever else is
+        in the batch and whatever ``max_grid`` (a bound on the kernel's
+        workgroups, 0 = the extension's cap) says. The words of a tensor
+        over the kernel's size cap are its dim-0 pieces' merged in order.
+        Statistics are of the live values: ``stored_dtypes`` is accepted
+        for state_checks.UniqueTensors.read and ignored. fp8, complex,
+        integer, quantized and sparse tensors report STATS_EMPTY.
+
+        Tensors build_stats_items() declines are computed with torch
+        expressions instead; so is everything when the extension is
+        disabled by TSAMD_DISABLE_HIP_STAGING=1."""
+        if not self._use_ext:
+            return [torch_tensor_stats(t) for t in tensors]
+        per_tensor, classes = build_stats_items(tensors)
+        columns = self._read_launch(
+            # without a class there is nothing to report, and no fallback
+            [[] if cls is None else its for its, cls in zip(per_tensor, classes)],
+            lambda items, owners, stream, dev_index: _csnap.tensor_stats(
+                _items_to_flat(items),
+                len(items),
+                [classes[i] for i in owners],
+                dev_index,
+                stream,
+                max_grid,
+            ),
+            6,
+            lambda i: torch_tensor_stats(tensors[i]),
+            merge=merge_stats,
+            empty=STATS_EMPTY,
+        )
+        return [list(row) for row in zip(*columns)] if tensors else []
+
+    # -- what the read-only launches share -----------------------------------
 
     def _read_launch(
         self,
@@ -1238,32 +1426,48 @@ class StagingEngine:
         call: Callable[..., Sequence[int]],
         words: int,
         fallback: Callable[[int], Sequence[int]],
+        merge: Optional[Callable[[Sequence[int], Sequence[int]], Sequence[int]]] = None,
+        empty: Optional[Sequence[int]] = None,
     ) -> List[List[int]]:
         """``words`` u64 results for each tensor of a batch, from ONE
         extension call over every descriptor in ``per_tensor``; returned
         as one list per word, each with an entry per tensor.
         ``call(items, owners, stream, dev_index)`` makes the call and
         returns ``words`` values per descriptor; ``owners[k]`` is the index
-        of the tensor that descriptor ``k`` belongs to. A tensor's result is
-        the sum of its descriptors' mod 2^64 (counts stay far below it),
-        zeros without descriptors. A None entry is a tensor the builder
-        declined: ``fallback(index)`` answers for it."""
+        of the tensor that descriptor ``k`` belongs to. A None entry is a
+        tensor the builder declined: ``fallback(index)`` answers for it.
+
+        A tensor's descriptors are combined in one of two ways. Without
+        ``merge`` its result is the sum of its descriptors' words mod 2^64
+        (counts stay far below it), zeros without descriptors. With
+        ``merge`` its result starts as ``empty`` and each descriptor's
+        words, in order, are folded in as
+        ``merge(so_far, words_of_descriptor)``."""
         items: List[PackItem] = []
         owners: List[int] = []
         for i, its in enumerate(per_tensor):
             for it in its or ():
                 items.append(it)
                 owners.append(i)
-        out = [[0] * len(per_tensor) for _ in range(words)]
+        out = [[e] * len(per_tensor) for e in (empty or [0] * words)]
         if items:
             dev_index = self.device.index or 0
             with torch.cuda.device(dev_index):
                 got = call(
                     items, owners, torch.cuda.current_stream().cuda_stream, dev_index
                 )
-            for w, column in enumerate(out):
-                for i, v in zip(owners, got[w::words]):
-                    column[i] = (column[i] + v) % (1 << 64)
+            if merge is None:
+                for w, column in enumerate(out):
+                    for i, v in zip(owners, got[w::words]):
+                        column[i] = (column[i] + v) % (1 << 64)
+            else:
+                for k, i in enumerate(owners):
+                    merged = merge(
+                        [column[i] for column in out],
+                        got[k * words : (k + 1) * words],
+                    )
+                    for column, v in zip(out, merged):
+                        column[i] = v
         for i, its in enumerate(per_tensor):
             if its is None:
                 for column, v in zip(out, fallback(i)):

@@ -32,7 +32,12 @@ from typing import Any, Dict, List, Optional, Set, Tuple, Union
 import torch
 import torch.distributed as dist
 
-from . import knobs, nonfinite as _nonfinite, replication as _replication
+from . import (
+    knobs,
+    nonfinite as _nonfinite,
+    replication as _replication,
+    tensor_stats as _tensor_stats,
+)
 from .dist_store import LinearBarrier, get_or_create_store
 from .event import Event, log_event
 from .flatten import Flattened, flatten, inflate
@@ -209,6 +214,22 @@ class Snapshot:
         """A deep copy of the global manifest as plain dicts."""
         return {k: v.to_dict() for k, v in self.metadata.manifest.items()}
 
+    def get_stats(self) -> Dict[str, "_tensor_stats.TensorStats"]:
+        """``{logical_path: TensorStats}`` as recorded by
+        ``take(..., stats=True)``; empty for a snapshot taken without."""
+        from .io_types import ReadIO
+
+        storage = url_to_storage_plugin(self.path, self._storage_options)
+        try:
+            read_io = ReadIO(path=_tensor_stats.SIDECAR_FILENAME)
+            try:
+                storage.sync_read(read_io)
+            except FileNotFoundError:
+                return {}
+            return _tensor_stats.decode_sidecar(bytes(read_io.buf))
+        finally:
+            storage.sync_close()
+
     def delete(self) -> None:
         """Delete the snapshot (metadata first, so a concurrent reader sees
         an invalid snapshot rather than a partially-deleted one)."""
@@ -242,6 +263,8 @@ class Snapshot:
         save_dtype: SaveDtype = None,
         nonfinite: Optional[str] = None,
         replicated_check: Optional[str] = None,
+        *,
+        stats: bool = False,
     ) -> "Snapshot":
         """``save_dtype``: store float32 tensors narrowed to
         ``torch.bfloat16`` / ``torch.float16`` — one dtype for everything,
@@ -265,7 +288,15 @@ class Snapshot:
         ``path`` is touched. ``"error"`` raises
         :class:`ReplicatedStateMismatchError` on every rank when a leaf
         differs and leaves an earlier snapshot at ``path`` intact;
-        ``"warn"`` logs the leaves and saves."""
+        ``"warn"`` logs the leaves and saves.
+
+        ``stats``: record count, zeros, minimum, maximum, sum and sum of
+        squares of the finite elements of every float64/32/16 and bfloat16
+        tensor leaf in a ``.tensor_stats`` sidecar beside the manifest
+        (:meth:`get_stats`). They are statistics of the live values, not of
+        a ``save_dtype`` narrowing; device tensors are read in place by one
+        kernel launch per device. Off by default: nothing runs and no
+        sidecar is written."""
         torch._C._log_api_usage_once("torchsnapshot_amd.Snapshot.take")
         cls._validate_app_state(app_state)
         save_dtype_rules = _normalize_save_dtype(save_dtype)
@@ -292,6 +323,7 @@ class Snapshot:
                     save_dtype_rules=save_dtype_rules,
                     nonfinite_policy=nonfinite_policy,
                     replicated_policy=replicated_policy,
+                    stats=stats,
                 )
                 pending_io_work.complete()
                 from .integrity import write_checksum_file
@@ -322,9 +354,11 @@ class Snapshot:
         save_dtype: SaveDtype = None,
         nonfinite: Optional[str] = None,
         replicated_check: Optional[str] = None,
+        *,
+        stats: bool = False,
     ) -> "PendingSnapshot":
-        """See :meth:`take` for ``save_dtype``, ``nonfinite`` and
-        ``replicated_check``; a :class:`NonFiniteStateError` or
+        """See :meth:`take` for ``save_dtype``, ``nonfinite``,
+        ``replicated_check`` and ``stats``; a :class:`NonFiniteStateError` or
         :class:`ReplicatedStateMismatchError` is raised here, not by the
         pending snapshot."""
         torch._C._log_api_usage_once("torchsnapshot_amd.Snapshot.async_take")
@@ -367,6 +401,7 @@ class Snapshot:
                 save_dtype_rules=save_dtype_rules,
                 nonfinite_policy=nonfinite_policy,
                 replicated_policy=replicated_policy,
+                stats=stats,
             )
             # once staging is complete, the app may mutate its state
             # freely. With shadow clones (sources_immutable) there is
@@ -408,6 +443,7 @@ class Snapshot:
         save_dtype_rules: Optional[List[Tuple[str, torch.dtype]]] = None,
         nonfinite_policy: str = "ignore",
         replicated_policy: str = "ignore",
+        stats: bool = False,
     ) -> Tuple[PendingIOWork, SnapshotMetadata]:
         rank = pg_wrapper.get_rank()
         world_size = pg_wrapper.get_world_size()
@@ -486,6 +522,12 @@ class Snapshot:
                 pg_wrapper,
             )
 
+        # statistics pass: the third reader of the state as it is about to
+        # be staged, beside the two checks. It refuses nothing; the ranks'
+        # reports are exchanged here, on the calling thread, and rank 0
+        # writes the merged result below once the old commit is gone.
+        collected = _tensor_stats.collect(flattened, pg_wrapper) if stats else None
+
         write_reqs: List[WriteReq] = []
         req_to_logical: Dict[str, str] = {}
         # tied-weight dedup: identical tensor objects (same storage, view,
@@ -551,7 +593,16 @@ class Snapshot:
         # plausible length. The manifest all-gather below orders this
         # before any rank's first payload write.
         if rank == 0:
-            cls._uncommit(storage)
+            cls._uncommit(storage, keep_stats=collected is not None)
+            if collected is not None:
+                # before .snapshot_metadata: a committed snapshot that asked
+                # for statistics has them
+                storage.sync_write(
+                    WriteIO(
+                        path=_tensor_stats.SIDECAR_FILENAME,
+                        buf=_tensor_stats.encode_sidecar(collected),
+                    )
+                )
 
         global_manifest = cls._gather_manifest(manifest, pg_wrapper)
         metadata = SnapshotMetadata(
@@ -568,19 +619,33 @@ class Snapshot:
         return pending, metadata
 
     @staticmethod
-    def _uncommit(storage: StoragePlugin) -> None:
+    def _uncommit(storage: StoragePlugin, keep_stats: bool = False) -> None:
         """Remove an existing ``.snapshot_metadata`` under a filesystem
         snapshot path (a missing one is fine). Object stores replace whole
         objects and never expose a half-written one, so only the FS plugin
-        needs this."""
+        needs this. The ``.tensor_stats`` sidecar of the old commit goes
+        with it, on any storage, unless this save is about to replace it
+        (``keep_stats``): statistics never outlive the state they are of."""
         from .storage.fs import FSStoragePlugin
 
         if not isinstance(storage, FSStoragePlugin):
+            if not keep_stats:
+                from .scheduler import run_coro_sync
+
+                try:
+                    run_coro_sync(storage.delete(_tensor_stats.SIDECAR_FILENAME))
+                except FileNotFoundError:
+                    # every plugin here reports a missing object this way
+                    # (the object stores' delete accepts a 404 itself); any
+                    # other failure would leave stale statistics beside the
+                    # new state, so it fails the save
+                    pass
             return
-        try:
-            os.remove(os.path.join(storage.root, METADATA_FILENAME))
-        except FileNotFoundError:
-            pass
+        for name in (_tensor_stats.SIDECAR_FILENAME, METADATA_FILENAME):
+            try:
+                os.remove(os.path.join(storage.root, name))
+            except FileNotFoundError:
+                pass
 
     @classmethod
     def _shadow_for_async(cls, flattened: Flattened) -> bool:
