@@ -8,6 +8,7 @@ budget; metadata coordination runs over RCCL (torch.distributed "nccl"
 backend on ROCm) or gloo.
 """
 
+from .compare import TensorDiff
 from .nonfinite import NonFiniteStateError, find_nonfinite
 from .replication import ReplicatedStateMismatchError, fingerprint_state
 from .rng_state import RNGState
@@ -30,5 +31,6 @@ __all__ = [
     "fingerprint_state",
     "TensorStats",
     "tensor_stats",
+    "TensorDiff",
     "__version__",
 ]

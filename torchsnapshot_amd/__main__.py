@@ -4,6 +4,8 @@
     python -m torchsnapshot_amd cat <path> <entry>   # print one object
     python -m torchsnapshot_amd stats <path> [--against <other>]
                                                      # recorded statistics
+    python -m torchsnapshot_amd compare <path> <other>
+                                                     # element-wise difference
 """
 
 from __future__ import annotations
@@ -126,6 +128,35 @@ def cmd_stats(args: argparse.Namespace) -> int:
     return 0
 
 
+def cmd_compare(args: argparse.Namespace) -> int:
+    """PATH against the tensors of OTHER, loaded to the host: one line per
+    differing path, largest relative error first (paths without one last)."""
+    from .state_dict import StateDict
+
+    other = Snapshot(args.other)
+    keys = sorted(
+        {k.partition("/")[2].partition("/")[0] for k in other.metadata.manifest}
+    )
+    state = {k: StateDict(other.get_state_dict_for_key(k)) for k in keys if k}
+    rows = []
+    for path, d in Snapshot(args.path).compare(state).items():
+        if d.equal:
+            continue
+        rel = d.rel_err if d.note is None else None
+        line = f"{path}: " + (
+            d.note
+            if d.note is not None
+            else f"n={d.n} n_diff={d.n_diff} n_nonfinite_diff={d.n_nonfinite_diff} "
+            f"max_abs={_fmt(d.max_abs)} rms_err={_fmt(d.rms_err)} "
+            f"rel_err={_fmt(rel)}"
+        )
+        rows.append((-1.0 if rel is None else rel, line))
+    rows.sort(key=lambda r: -r[0])
+    for _, line in rows:
+        print(line)
+    return 1 if rows else 0
+
+
 def main(argv=None) -> int:
     parser = argparse.ArgumentParser(prog="python -m torchsnapshot_amd")
     sub = parser.add_subparsers(dest="cmd", required=True)
@@ -148,6 +179,12 @@ def main(argv=None) -> int:
         "snapshot at OTHER, largest first",
     )
     p_stats.set_defaults(fn=cmd_stats)
+    p_compare = sub.add_parser(
+        "compare", help="compare a snapshot with another, element by element"
+    )
+    p_compare.add_argument("path")
+    p_compare.add_argument("other")
+    p_compare.set_defaults(fn=cmd_compare)
     args = parser.parse_args(argv)
     return args.fn(args)
 

@@ -30,7 +30,11 @@ from .io_types import (
     StageContext,
     WriteReq,
 )
-from .io_preparers.pinned_read import PinnedReadConsumer, payload_to_device
+from .io_preparers.pinned_read import (
+    PinnedReadConsumer,
+    compare_on_device,
+    payload_to_device,
+)
 from .io_preparers.tensor import TensorBufferStager
 from .ops.staging import (
     ALIGN,
@@ -329,7 +333,11 @@ class BatchedBufferConsumer(PinnedReadConsumer):
 
     def will_verify_on_device(self) -> bool:
         # with or without a pinned block: the whole span goes to the device
-        return HIP_EXT_AVAILABLE and self._device_fast_path_target() is not None
+        return (
+            HIP_EXT_AVAILABLE
+            and getattr(self.members[0].consumer, "compare", None) is None
+            and self._device_fast_path_target() is not None
+        )
 
     async def consume_buffer(self, ctx: StageContext, buf: BufferType) -> None:
         device = self._device_fast_path_target()
@@ -341,7 +349,24 @@ class BatchedBufferConsumer(PinnedReadConsumer):
                 await m.consumer.consume_buffer(ctx, sub)
             return
 
+        def compare() -> None:
+            # the compare action: every member of the span in ONE launch of
+            # the compare kernel, out of the pinned block where there is one
+            pairs = []
+            for m in self.members:
+                pairs += m.consumer.compare_members(m.byte_range[0] - self.span_start)
+            span_u8 = compare_on_device(
+                self, buf, device, pairs, f"{self.members[0].path} span"
+            )
+            for m in self.members:
+                s, e = m.byte_range
+                m.consumer.compare_rest(
+                    span_u8[s - self.span_start : e - self.span_start]
+                )
+
         def work() -> None:
+            if self.members[0].consumer.compare is not None:
+                return compare()
             # the whole span in ONE scatter launch, or one H2D sliced on
             # the GPU per member
             dev_span = payload_to_device(

@@ -3,7 +3,7 @@ bound for device tensors from there (or from a plain buffer) to the GPU."""
 
 from __future__ import annotations
 
-from typing import Optional, Sequence, Tuple
+from typing import Any, Optional, Sequence, Tuple
 
 import torch
 
@@ -19,6 +19,10 @@ class PinnedReadConsumer(BufferConsumer):
 
     _pinned_block = None
     _pinned_nbytes = 0
+    # a compare.CompareAction: the consumer then compares the payload with
+    # its target where it would have written it (Snapshot.compare), and
+    # leaves the checksum to the scheduler's host-side check
+    compare = None
 
     def alloc_pinned_buffer(self, nbytes: int) -> memoryview:
         self._pinned_block = get_pinned_pool().acquire(max(nbytes, 1))
@@ -80,3 +84,38 @@ def payload_to_device(
     if expected_psum is not None:
         verify_device_psum(dev_u8, expected_psum, what)
     return dev_u8
+
+
+def compare_on_device(
+    consumer: PinnedReadConsumer,
+    buf: BufferType,
+    device: torch.device,
+    members: Sequence[Tuple[Tuple[torch.Tensor, torch.dtype, int], Any, int]],
+    what: str,
+) -> torch.Tensor:
+    """The ladder under the compare action: the payload against
+    ``members``, each ``(engine member, compare action, key offset)`` with a
+    live tensor on ``device``; the fields found are added to the member's
+    action. Returns the payload as a uint8 tensor, where the ladder left it.
+
+    (a) The read landed in the consumer's pinned block: ONE
+        StagingEngine.compare launch reads the block in place; no
+        payload-sized device memory is made.
+    (b)/(c) as in payload_to_device(): the payload goes to the device
+        first, and the same launch reads it there.
+
+    The engine answers for the members its kernel declines with the torch
+    expression. The choice does not look at TSAMD_RESTORE_MODE, which
+    records a throughput decision about restores that write."""
+    block, n = consumer._pinned_block, consumer._pinned_nbytes
+    engine = get_staging_engine(device)
+    triples = [m for m, _, _ in members]
+    if block is not None:
+        flat_u8 = block.tensor[:n]
+        found = engine.compare(block, n, triples)
+    else:
+        flat_u8 = payload_to_device(consumer, buf, device, None, None, what)
+        found = engine.compare(flat_u8, flat_u8.numel(), triples)
+    for (_, action, key_off), fields in zip(members, found):
+        action.add(key_off, fields)
+    return flat_u8

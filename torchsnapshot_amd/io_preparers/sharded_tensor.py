@@ -27,7 +27,7 @@ from ..io_types import (
 )
 from ..manifest import Shard as ShardMeta
 from ..manifest import ShardedTensorEntry, TensorEntry
-from ..ops.staging import HIP_EXT_AVAILABLE, scatter_member
+from ..ops.staging import HIP_EXT_AVAILABLE, scatter_member, torch_tensor_diff
 from ..serialization import (
     SERIALIZER_BUFFER,
     dtype_to_str,
@@ -35,7 +35,12 @@ from ..serialization import (
     tensor_from_memoryview,
     torch_load_from_bytes,
 )
-from .pinned_read import PinnedReadConsumer, payload_to_device, view_payload
+from .pinned_read import (
+    PinnedReadConsumer,
+    compare_on_device,
+    payload_to_device,
+    view_payload,
+)
 from .tensor import LoadFuture, TensorIOPreparer, tensor_copy
 
 logger = logging.getLogger(__name__)
@@ -167,9 +172,41 @@ class ShardConsumer(PinnedReadConsumer):
         # only the pinned -> device path checksums on the GPU
         return (
             HIP_EXT_AVAILABLE
+            and self.compare is None
             and self._pinned_block is not None
             and self.device_span_target() is not None
         )
+
+    def compare_members(self, base_offset: int):
+        """compare_on_device() members: every overlap whose source box is
+        one contiguous run of the stored shard, keyed by the run's byte
+        offset in it. compare_rest() answers for the others."""
+        stored = str_to_dtype(self.shard_entry.dtype)
+        members = []
+        for dst_view, ov in self.targets:
+            src_off = contiguous_source_offset(self.shard_entry.shape, ov)
+            if src_off is not None:
+                dst = narrow_nd(dst_view.detach(), ov.dst_offsets, ov.lengths)
+                off = src_off * stored.itemsize
+                members.append(((dst, stored, base_offset + off), self.compare, off))
+        return members
+
+    def compare_rest(self, flat_u8: torch.Tensor) -> None:
+        """The overlaps whose source box is a general sub-box of the stored
+        shard, by the torch expression, keyed by the box's first byte."""
+        stored = str_to_dtype(self.shard_entry.dtype)
+        shard = None
+        for dst_view, ov in self.targets:
+            if contiguous_source_offset(self.shard_entry.shape, ov) is None:
+                if shard is None:
+                    shard = view_payload(flat_u8, stored, self.shard_entry.shape)
+                self._compare_overlap(shard, dst_view, ov)
+
+    def _compare_overlap(self, shard: torch.Tensor, dst_view, ov: Overlap) -> None:
+        src = narrow_nd(shard, ov.src_offsets, ov.lengths)
+        dst = narrow_nd(dst_view, ov.dst_offsets, ov.lengths)
+        off = src.storage_offset() - shard.storage_offset()
+        self.compare.add(off * shard.element_size(), torch_tensor_diff(src, dst))
 
     def scatter_members(self, base_offset: int, verified: bool = False):
         """Every overlap's source box has to be a contiguous run of the
@@ -219,6 +256,17 @@ class ShardConsumer(PinnedReadConsumer):
         def work() -> None:
             if self.shard_entry.serializer == "torch_save":
                 shard = torch_load_from_bytes(bytes(buf))
+            elif self.compare is not None and self.all_targets_on_device():
+                self.compare_rest(
+                    compare_on_device(
+                        self,
+                        buf,
+                        self.targets[0][0].device,
+                        self.compare_members(0),
+                        self.shard_entry.location,
+                    )
+                )
+                return
             elif self.all_targets_on_device():
                 verified = self.expected_psum is not None
                 dev_u8 = payload_to_device(
@@ -240,6 +288,10 @@ class ShardConsumer(PinnedReadConsumer):
                     dtype=str_to_dtype(self.shard_entry.dtype),
                     shape=tuple(self.shard_entry.shape),
                 )
+            if self.compare is not None:
+                for dst_view, ov in self.targets:
+                    self._compare_overlap(shard, dst_view, ov)
+                return
             self._copy_overlaps(shard)
 
         await asyncio.get_running_loop().run_in_executor(ctx.executor, work)

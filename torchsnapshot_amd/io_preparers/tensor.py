@@ -32,6 +32,7 @@ from ..ops.staging import (
     get_staging_engine,
     resolve_lazy,
     scatter_member,
+    torch_tensor_diff,
 )
 from ..serialization import (
     SERIALIZER_BUFFER,
@@ -47,7 +48,12 @@ from ..serialization import (
     torch_load_from_bytes,
     torch_save_as_bytes,
 )
-from .pinned_read import PinnedReadConsumer, payload_to_device, view_payload
+from .pinned_read import (
+    PinnedReadConsumer,
+    compare_on_device,
+    payload_to_device,
+    view_payload,
+)
 
 
 class LoadFuture:
@@ -408,9 +414,19 @@ class TensorBufferConsumer(PinnedReadConsumer):
         # only the pinned -> device path checksums on the GPU
         return (
             HIP_EXT_AVAILABLE
+            and self.compare is None
             and self._pinned_block is not None
             and self.device_span_target() is not None
         )
+
+    def compare_members(self, base_offset: int):
+        """The one compare_on_device() member: the whole target against the
+        payload at ``base_offset`` of the read."""
+        stored = str_to_dtype(self.entry.dtype)
+        return [((self.tensor_out.detach(), stored, base_offset), self.compare, 0)]
+
+    def compare_rest(self, flat_u8: torch.Tensor) -> None:
+        """compare_members() covers the payload."""
 
     def scatter_members(self, base_offset: int, verified: bool = False):
         """The one member covers the payload exactly once, which is what a
@@ -442,6 +458,11 @@ class TensorBufferConsumer(PinnedReadConsumer):
                 loaded = qtensor_from_bytes(buf)
             elif self.entry.serializer == SERIALIZER_TORCH_SAVE:
                 loaded = torch_load_from_bytes(bytes(buf))
+            elif self.compare is not None and self.device_span_target() is not None:
+                compare_on_device(
+                    self, buf, out.device, self.compare_members(0), self.entry.location
+                )
+                return
             elif out is not None and out.device.type == "cuda":
                 dev_u8 = payload_to_device(
                     self,
@@ -463,7 +484,9 @@ class TensorBufferConsumer(PinnedReadConsumer):
                     dtype=str_to_dtype(self.entry.dtype),
                     shape=tuple(self.entry.shape),
                 )
-            if out is not None:
+            if self.compare is not None:
+                self.compare.add(0, torch_tensor_diff(loaded, out))
+            elif out is not None:
                 tensor_copy(out, loaded)
                 self.fut.obj = out
             else:

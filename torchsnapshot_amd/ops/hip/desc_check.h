@@ -9,9 +9,10 @@
 //
 // Every entry point of the extension that takes descriptor rows -
 // pack_d2h, scatter_h2d, unpack_h2d, scan_nonfinite, fingerprint_tensors,
-// tensor_stats - runs check_descs before it touches the GPU: a row that would make a
-// kernel issue a misaligned vector access, index past its rows, or wrap a
-// u32 index is a std::runtime_error here, not a device fault there.
+// tensor_stats, compare_tensors - runs check_descs before it touches the GPU:
+// a row that would make a kernel issue a misaligned vector access, index
+// past its rows, or wrap a u32 index is a std::runtime_error here, not a
+// device fault there.
 
 #pragma once
 
@@ -81,6 +82,33 @@ constexpr uint32_t scan_elem_size(uint32_t cls) {
                                                  : 1u;
 }
 
+// element classes of the compare kernel (CMP_* in ops/staging.py). The first
+// four are the scan's float classes, stored and live of one dtype; the raw
+// classes compare bit patterns only, by element size; the last two have a
+// 16-bit stored side and a float32 live side (descriptor cast codes 3 and 4)
+constexpr uint32_t kCmpRaw1 = 4;
+constexpr uint32_t kCmpRaw2 = 5;
+constexpr uint32_t kCmpRaw4 = 6;
+constexpr uint32_t kCmpRaw8 = 7;
+constexpr uint32_t kCmpRaw16 = 8;
+constexpr uint32_t kCmpBF16toF32 = 9;
+constexpr uint32_t kCmpF16toF32 = 10;
+constexpr uint32_t kCmpClasses = 11;
+
+// stored (flat-side) element size of a compare class
+constexpr uint32_t cmp_elem_size(uint32_t cls) {
+  return cls <= kScanBF16 ? scan_elem_size(cls)
+         : cls >= kCmpBF16toF32 ? 2u
+                                : 1u << (cls - kCmpRaw1);
+}
+
+// the descriptor cast code a compare class goes with
+constexpr uint32_t cmp_cast_code(uint32_t cls) {
+  return cls == kCmpBF16toF32  ? kCastBF16toF32
+         : cls == kCmpF16toF32 ? kCastF16toF32
+                               : kCastNone;
+}
+
 // flat desc rows from python: 19 u64 each (see ops/staging.py)
 constexpr int kRowInts = 19;
 
@@ -131,9 +159,13 @@ enum class DescKind {
                 // offset and must be a multiple of vec
   Stats,    // tensor_stats: no cast code; one class per descriptor, below
             // kStatsClasses
+  Compare,  // compare_tensors: one kCmp* class per descriptor and the cast
+            // code that goes with it; needs a FlatSide (pinned_ptr is the
+            // payload's address, on the host or on the device)
 };
 
-// unpack_h2d's flat side: where the payload sits and how long it is
+// unpack_h2d's and compare_tensors' flat side: where the payload sits and
+// how long it is
 struct FlatSide {
   uintptr_t slab_ptr = 0;
   uintptr_t pinned_ptr = 0;
@@ -161,6 +193,7 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
                           : kind == DescKind::Unpack  ? "unpack_h2d: "
                           : kind == DescKind::Scan    ? "scan_nonfinite: "
                           : kind == DescKind::Stats   ? "tensor_stats: "
+                          : kind == DescKind::Compare ? "compare_tensors: "
                                                       : "fingerprint_tensors: ";
   auto refuse = [&who](const char* what) {
     throw std::runtime_error(who + what);
@@ -170,7 +203,11 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
     if (flat->hash_byte0 % 8 != 0) refuse("hash_byte0 must be 8-aligned");
     if (flat->slab_ptr % 16 != 0) refuse("slab must be 16-aligned");
   }
-  const bool classed = kind == DescKind::Scan || kind == DescKind::Stats;
+  const bool flat_sided =
+      kind == DescKind::Unpack || kind == DescKind::Compare;
+  if (kind == DescKind::Compare && flat == nullptr) refuse("no flat side given");
+  const bool classed = kind == DescKind::Scan || kind == DescKind::Stats ||
+                       kind == DescKind::Compare;
   if (classed && (classes == nullptr || classes->size() != descs.size())) {
     refuse("one class code per descriptor");
   }
@@ -205,12 +242,18 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
         if ((*classes)[i] >= kStatsClasses) refuse("unknown element class");
         if (cast) refuse("cast descriptors not allowed");
         break;
+      case DescKind::Compare:
+        if ((*classes)[i] >= kCmpClasses) refuse("unknown element class");
+        if (d.cast != cmp_cast_code((*classes)[i])) {
+          refuse("cast code does not go with the element class");
+        }
+        break;
     }
     if (d.nbytes == 0) continue;
     if (d.nbytes > kMaxDescBytes) {
       refuse("tensor too large (> 4 GiB - 64 KiB)");
     }
-    if (kind == DescKind::Unpack &&
+    if (flat_sided &&
         (d.flat_off > flat->total_bytes ||
          d.nbytes > flat->total_bytes - d.flat_off)) {
       refuse("descriptor outside the payload");
@@ -220,14 +263,16 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
       refuse(cast ? "cast descriptor: vec must be 16/8/4/2"
                   : "vec must be 16/8/4/2/1");
     }
-    if (classed && v < scan_elem_size((*classes)[i])) {
+    if (classed && v < (kind == DescKind::Compare
+                            ? cmp_elem_size((*classes)[i])
+                            : scan_elem_size((*classes)[i]))) {
       refuse("vec below the element size");
     }
     if (d.row_bytes == 0 || d.row_bytes % v != 0 ||
         d.nbytes % d.row_bytes != 0) {
       refuse("row_bytes/vec mismatch");
     }
-    if (kind == DescKind::Unpack && (flat->pinned_ptr + d.flat_off) % v != 0) {
+    if (flat_sided && (flat->pinned_ptr + d.flat_off) % v != 0) {
       refuse("flat address not aligned for its vec");
     }
     if (kind == DescKind::Fingerprint && d.flat_off % v != 0) {

@@ -18,6 +18,10 @@
 //   - stats kernel: count, zeros, min, max, sum and sum of squares of each
 //     tensor's finite elements in f64, read in place over the same
 //     descriptors, with sums that are bit-identical for any grid (stats=)
+//   - compare kernel: a stored payload, read in place from pinned host
+//     memory or from HBM, against the live strided tensors element by
+//     element; both sides read-only, six words per tensor, the f64 sums
+//     through the stats kernel's two-stage reduction (Snapshot.compare)
 //   - SDMA copies (hipMemcpyAsync) slab <-> pinned host memory; the slab
 //     can also be skipped entirely ("direct" mode): the kernel writes
 //     gathered bytes straight into pinned host memory over PCIe
@@ -1101,6 +1105,48 @@ __device__ __forceinline__ double wave_sum_fixed(double v) {
   return v;
 }
 
+// Stage one of a pair of two-stage f64 sums, shared by the stats and the
+// compare kernel: the fixed tree per wave, the four wave results through
+// `wave_sums` in wave order, and the unit's pair stored at partials[2 * wu].
+// Every thread of the workgroup must call it (two barriers).
+__device__ __forceinline__ void store_unit_sums(
+    double (*wave_sums)[2], double* __restrict__ partials,
+    unsigned long long wu, double a, double b) {
+  const double wa = wave_sum_fixed(a);
+  const double wb = wave_sum_fixed(b);
+  if ((threadIdx.x & 63) == 0) {
+    wave_sums[threadIdx.x >> 6][0] = wa;
+    wave_sums[threadIdx.x >> 6][1] = wb;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double ua = wave_sums[0][0], ub = wave_sums[0][1];
+    for (int w = 1; w < kBlockThreads / 64; ++w) {
+      ua = __dadd_rn(ua, wave_sums[w][0]);
+      ub = __dadd_rn(ub, wave_sums[w][1]);
+    }
+    partials[2 * wu] = ua;
+    partials[2 * wu + 1] = ub;
+  }
+  __syncthreads();  // before the next unit's waves overwrite the LDS
+}
+
+// Stage two, for one wave: lane l adds the pairs of work units first + l,
+// first + l + 64, ... below `end` in that order, the fixed tree follows,
+// and lane 0 holds the two sums.
+__device__ __forceinline__ void finish_unit_sums(
+    const double* __restrict__ partials, unsigned long long first,
+    unsigned long long end, double& a, double& b) {
+  a = 0.0;
+  b = 0.0;
+  for (unsigned long long wu = first + threadIdx.x; wu < end; wu += 64) {
+    a = __dadd_rn(a, partials[2 * wu]);
+    b = __dadd_rn(b, partials[2 * wu + 1]);
+  }
+  a = wave_sum_fixed(a);
+  b = wave_sum_fixed(b);
+}
+
 // wave64 min / max of the keys and one atomic per wave; none for a wave
 // that saw no finite element
 __device__ __forceinline__ void minmax_per_wave(unsigned long long* out,
@@ -1161,24 +1207,8 @@ __global__ __launch_bounds__(kBlockThreads) void stats_kernel(
         kmax = a.kmax;
         // stage one of the sums. The owner, and so the path to here, is
         // uniform across the workgroup: every thread reaches both barriers
-        const double ws = wave_sum_fixed(a.sum);
-        const double wq = wave_sum_fixed(a.sumsq);
-        if ((threadIdx.x & 63) == 0) {
-          wave_sums[threadIdx.x >> 6][0] = ws;
-          wave_sums[threadIdx.x >> 6][1] = wq;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-          double us = wave_sums[0][0], uq = wave_sums[0][1];
-          for (int w = 1; w < kBlockThreads / 64; ++w) {
-            us = __dadd_rn(us, wave_sums[w][0]);
-            uq = __dadd_rn(uq, wave_sums[w][1]);
-          }
-          const unsigned long long wu = wu_prefix[owner] + s / kWorkUnitBytes;
-          partials[2 * wu] = us;
-          partials[2 * wu + 1] = uq;
-        }
-        __syncthreads();  // before the next unit's waves overwrite the LDS
+        store_unit_sums(wave_sums, partials,
+                        wu_prefix[owner] + s / kWorkUnitBytes, a.sum, a.sumsq);
       });
   if (cur >= 0) flush();
 }
@@ -1191,17 +1221,343 @@ __global__ __launch_bounds__(64) void stats_finish_kernel(
     const double* __restrict__ partials, unsigned long long* __restrict__ out) {
   const int i = blockIdx.x;
   if (i >= n) return;
-  const unsigned long long end = wu_prefix[i + 1];
-  double s = 0.0, q = 0.0;
-  for (unsigned long long wu = wu_prefix[i] + threadIdx.x; wu < end; wu += 64) {
-    s = __dadd_rn(s, partials[2 * wu]);
-    q = __dadd_rn(q, partials[2 * wu + 1]);
-  }
-  s = wave_sum_fixed(s);
-  q = wave_sum_fixed(q);
+  double s, q;
+  finish_unit_sums(partials, wu_prefix[i], wu_prefix[i + 1], s, q);
   if (threadIdx.x == 0) {
     out[6 * i + 4] = (unsigned long long)__double_as_longlong(s);
     out[6 * i + 5] = (unsigned long long)__double_as_longlong(q);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// compare: a stored payload against live tensors, element by element, with
+// BOTH sides read-only. The flat side is the payload where the storage read
+// put it (the consumer's pinned host block, read once over PCIe, or a device
+// buffer); the tensor side is the live strided tensor. Unpack-style
+// descriptors (flat_off inside the payload, vec that divides the flat
+// address too, cast codes 0, 3 and 4) and one kCmp* class per descriptor
+// beside them. Six u64 words per descriptor:
+//
+//   0  n, elements compared (host)   3  max |v - s|, f64 bits
+//   1  n_diff, bit patterns differ   4  sum (v - s)^2, f64 bits
+//   2  n_nonfinite_diff              5  sum s^2, f64 bits
+//
+// s is the stored element brought to the live dtype (bf16/f16 stored against
+// f32 live widen with the restore's bit arithmetic), v the live one; both
+// widen to f64 exactly, on the bit patterns, as in the stats kernel. Words
+// 3-5 are over the pairs with both sides finite; a differing pair with a
+// non-finite side counts in word 2. The raw classes (integers, bool, fp8,
+// complex: compared bitwise per element) fill words 0 and 1 only.
+//
+//   - work split: the stats kernel's. 64 KiB of STORED bytes per workgroup
+//     pass, lanes across a contiguous run or a wide row, one lane per
+//     narrow row; TS = 2 for the widen classes
+//   - lane operation: one naturally aligned VEC-byte load of the flat side
+//     and the matching load(s) of the tensor side into registers, the stored
+//     words brought to the live format, and a whole-word comparison first.
+//     A vector whose words all agree only adds to word 5; otherwise every
+//     element is classified and accumulated without a branch (a non-finite
+//     pair contributes 0.0 to the sums and 0 to the maximum). Both paths add
+//     the same terms in the same order: d = v - v is +0.0 and its square
+//     leaves a non-negative sum as it is. A load narrower than a word is
+//     zero-padded on both sides, and a pair of zeros changes no word
+//   - words 1-3 are carried from one work unit to the next while the
+//     workgroup stays on one descriptor, then add_per_wave for the counters
+//     and a wave64 shuffle max with ONE atomicMax per wave for word 3: the
+//     u64 pattern of a non-negative f64 is monotone in its value
+//   - words 4-5 go through the fixed-shape two-stage reduction of the stats
+//     kernel (store_unit_sums, then compare_finish_kernel on the same
+//     stream): no word depends on the grid, the order of workgroups or the
+//     descriptor's place in the batch
+// ---------------------------------------------------------------------------
+
+struct CmpLane {
+  uint32_t n_diff = 0, n_nonfinite = 0;
+  unsigned long long kmax = 0ull;
+  double sq = 0.0, ref = 0.0;
+};
+
+// one pair with equal bits: only the reference sum moves
+__device__ __forceinline__ void cmp_same(unsigned long long sb, bool finite,
+                                         CmpLane& a) {
+  const double s = finite ? __longlong_as_double((long long)sb) : 0.0;
+  a.ref = __dadd_rn(a.ref, __dmul_rn(s, s));
+}
+
+// one pair, given as f64 patterns, whether each side is finite and whether
+// the native bit patterns differ
+__device__ __forceinline__ void cmp_pair(unsigned long long sb, bool s_fin,
+                                         unsigned long long vb, bool v_fin,
+                                         bool differ, CmpLane& a) {
+  const bool both = s_fin & v_fin;
+  a.n_diff += differ;
+  a.n_nonfinite += differ & !both;
+  const double s = both ? __longlong_as_double((long long)sb) : 0.0;
+  const double v = both ? __longlong_as_double((long long)vb) : 0.0;
+  const double d = __dsub_rn(v, s);
+  const unsigned long long k =
+      (unsigned long long)__double_as_longlong(d) & 0x7FFFFFFFFFFFFFFFull;
+  a.kmax = k > a.kmax ? k : a.kmax;
+  a.sq = __dadd_rn(a.sq, __dmul_rn(d, d));
+  a.ref = __dadd_rn(a.ref, __dmul_rn(s, s));
+}
+
+__device__ __forceinline__ bool f32_finite(uint32_t u) {
+  return (u & 0x7FFFFFFFu) < 0x7F800000u;
+}
+
+// V bytes (16/8/4/2/1, naturally aligned) into w[0..3], zero-padded
+template <int V>
+__device__ __forceinline__ void load_words(const char* p, uint32_t* w) {
+  w[0] = w[1] = w[2] = w[3] = 0u;
+  if (V == 16) {
+    const uint4 a = *reinterpret_cast<const uint4*>(p);
+    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
+  } else if (V == 8) {
+    const uint2 a = *reinterpret_cast<const uint2*>(p);
+    w[0] = a.x; w[1] = a.y;
+  } else if (V == 4) {
+    w[0] = *reinterpret_cast<const uint32_t*>(p);
+  } else if (V == 2) {
+    w[0] = *reinterpret_cast<const uint16_t*>(p);
+  } else {
+    w[0] = *reinterpret_cast<const unsigned char*>(p);
+  }
+}
+
+// the elements of one word of the live format: stored word s, live word t.
+// SAME: the caller found every word of the vector equal
+template <uint32_t CLS, bool SAME>
+__device__ __forceinline__ void cmp_word(uint32_t s, uint32_t t, CmpLane& a) {
+  if (CLS == kScanF32) {
+    if (SAME) {
+      cmp_same(f32_to_f64_bits(s), f32_finite(s), a);
+    } else {
+      cmp_pair(f32_to_f64_bits(s), f32_finite(s), f32_to_f64_bits(t),
+               f32_finite(t), s != t, a);
+    }
+  } else {  // two 16-bit elements; inf and NaN stay inf and NaN in f32
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const uint32_t sh = (s >> (16 * h)) & 0xFFFFu;
+      const uint32_t th = (t >> (16 * h)) & 0xFFFFu;
+      const uint32_t s32 =
+          CLS == kScanBF16 ? bf16_to_f32_bits(sh) : f16_to_f32_bits(sh);
+      if (SAME) {
+        cmp_same(f32_to_f64_bits(s32), f32_finite(s32), a);
+      } else {
+        const uint32_t t32 =
+            CLS == kScanBF16 ? bf16_to_f32_bits(th) : f16_to_f32_bits(th);
+        cmp_pair(f32_to_f64_bits(s32), f32_finite(s32), f32_to_f64_bits(t32),
+                 f32_finite(t32), sh != th, a);
+      }
+    }
+  }
+}
+
+template <bool SAME>
+__device__ __forceinline__ void cmp_f64(uint32_t slo, uint32_t shi,
+                                        uint32_t tlo, uint32_t thi,
+                                        CmpLane& a) {
+  const unsigned long long sb = ((unsigned long long)shi << 32) | slo;
+  const unsigned long long tb = ((unsigned long long)thi << 32) | tlo;
+  const bool s_fin = (sb & 0x7FFFFFFFFFFFFFFFull) < 0x7FF0000000000000ull;
+  if (SAME) {
+    cmp_same(sb, s_fin, a);
+  } else {
+    const bool t_fin = (tb & 0x7FFFFFFFFFFFFFFFull) < 0x7FF0000000000000ull;
+    cmp_pair(sb, s_fin, tb, t_fin, sb != tb, a);
+  }
+}
+
+// number of elements of ESZ bytes that are non-zero in the NW words of x
+// (the XOR of the two sides)
+template <uint32_t ESZ, int NW>
+__device__ __forceinline__ uint32_t raw_diff_count(const uint32_t* x) {
+  uint32_t n = 0;
+  if (ESZ == 1 || ESZ == 2) {
+    // top bit of each element set where the element is non-zero
+    const uint32_t low = ESZ == 1 ? 0x7F7F7F7Fu : 0x7FFF7FFFu;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+      n += __popc((((x[i] & low) + low) | x[i]) & ~low);
+    }
+  } else {
+    constexpr int WPE = ESZ / 4;  // words per element
+#pragma unroll
+    for (int i = 0; i < NW; i += WPE) {
+      uint32_t any = 0;
+#pragma unroll
+      for (int k = 0; k < WPE; ++k) any |= x[i + k];
+      n += any != 0u;
+    }
+  }
+  return n;
+}
+
+// One flat vector of VEC stored bytes against the tensor bytes it stands
+// for (VEC of them, 2*VEC under a widen class).
+template <int VEC, uint32_t CLS>
+__device__ __forceinline__ void compare_vec(const char* flat, const char* ten,
+                                            CmpLane& a) {
+  constexpr bool WIDEN = CLS == kCmpBF16toF32 || CLS == kCmpF16toF32;
+  constexpr int FW = VEC >= 4 ? VEC / 4 : 1;  // flat words
+  constexpr int NW = WIDEN ? 2 * FW : FW;     // words of the live format
+  uint32_t f[4], s[8], t[8];
+  load_words<VEC>(flat, f);
+  if constexpr (WIDEN) {
+    // the restore's widening, on the registers just loaded
+#pragma unroll
+    for (int i = 0; i < FW; ++i) {
+      const uint2 p = widen_pair(f[i], cmp_cast_code(CLS));
+      s[2 * i] = p.x;
+      s[2 * i + 1] = p.y;
+    }
+    if constexpr (VEC == 16) {
+      load_words<16>(ten, t);
+      load_words<16>(ten + 16, t + 4);
+    } else {
+      load_words<2 * VEC>(ten, t);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < FW; ++i) s[i] = f[i];
+    load_words<VEC>(ten, t);
+  }
+  uint32_t x[NW];
+  uint32_t any = 0;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) {
+    x[i] = s[i] ^ t[i];
+    any |= x[i];
+  }
+  if constexpr (CLS >= kCmpRaw1 && CLS <= kCmpRaw16) {
+    a.n_diff += raw_diff_count<cmp_elem_size(CLS), NW>(x);
+  } else if constexpr (CLS == kScanF64) {
+    if (any == 0u) {
+#pragma unroll
+      for (int i = 0; i < NW; i += 2) cmp_f64<true>(s[i], s[i + 1], 0, 0, a);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NW; i += 2) {
+        cmp_f64<false>(s[i], s[i + 1], t[i], t[i + 1], a);
+      }
+    }
+  } else {
+    constexpr uint32_t LIVE = WIDEN ? kScanF32 : CLS;
+    if (any == 0u) {
+#pragma unroll
+      for (int i = 0; i < NW; ++i) cmp_word<LIVE, true>(s[i], 0, a);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NW; ++i) cmp_word<LIVE, false>(s[i], t[i], a);
+    }
+  }
+}
+
+// The class switch sits outside the traversal, as in scan_class; the host
+// refuses vec below the stored element size, so those pairs are not
+// instantiated.
+template <uint32_t CLS>
+__device__ __forceinline__ void compare_class(const Desc& d, const char* flat,
+                                              uint32_t s, uint32_t e,
+                                              CmpLane& a) {
+  constexpr uint32_t ESZ = cmp_elem_size(CLS);
+  constexpr int TS = cmp_cast_code(CLS) != kCastNone ? 2 : 1;
+  auto range = [&](auto vec) {
+    constexpr int VEC = decltype(vec)::value;
+    for_each_vec<VEC, TS>(d, s, e, [&](unsigned long long i, const char* p) {
+      compare_vec<VEC, CLS>(flat + i, p, a);
+    });
+  };
+  switch (d.vec) {
+    case 16: range(std::integral_constant<int, 16>{}); break;
+    case 8:
+      if constexpr (ESZ <= 8) range(std::integral_constant<int, 8>{});
+      break;
+    case 4:
+      if constexpr (ESZ <= 4) range(std::integral_constant<int, 4>{});
+      break;
+    case 2:
+      if constexpr (ESZ <= 2) range(std::integral_constant<int, 2>{});
+      break;
+    default:
+      if constexpr (ESZ <= 1) range(std::integral_constant<int, 1>{});
+      break;
+  }
+}
+
+// out[6*i ..]: the six words of descriptor i, zeroed by the launcher; word 0
+// is the host's and words 4-5 are left to compare_finish_kernel.
+// partials[2*wu], partials[2*wu + 1]: the two sums of work unit wu, every
+// one of which is written exactly once.
+__global__ __launch_bounds__(kBlockThreads) void compare_kernel(
+    const Desc* __restrict__ descs, const uint32_t* __restrict__ classes,
+    int n, const unsigned long long* __restrict__ wu_prefix,
+    unsigned long long total_wus, const char* __restrict__ flat_base,
+    unsigned long long* __restrict__ out, double* __restrict__ partials) {
+  __shared__ double wave_sums[kBlockThreads / 64][2];
+  unsigned long long n_diff = 0, n_nonfinite = 0, kmax = 0;
+  int cur = -1;
+  auto flush = [&]() {
+    add_per_wave(&out[6 * cur + 1], n_diff);
+    add_per_wave(&out[6 * cur + 2], n_nonfinite);
+    for (int delta = 32; delta > 0; delta >>= 1) {
+      const unsigned long long o = __shfl_down(kmax, delta, 64);
+      kmax = o > kmax ? o : kmax;
+    }
+    if ((threadIdx.x & 63) == 0 && kmax != 0ull) {
+      atomicMax(&out[6 * cur + 3], kmax);
+    }
+  };
+  for_each_work_unit(
+      descs, n, wu_prefix, total_wus,
+      [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
+        if (owner != cur) {
+          if (cur >= 0) flush();
+          n_diff = n_nonfinite = kmax = 0;
+          cur = owner;
+        }
+        CmpLane a;
+        a.kmax = kmax;
+        const char* flat = flat_base + d.flat_off;
+        switch (classes[owner]) {
+          case kScanF64: compare_class<kScanF64>(d, flat, s, e, a); break;
+          case kScanF32: compare_class<kScanF32>(d, flat, s, e, a); break;
+          case kScanF16: compare_class<kScanF16>(d, flat, s, e, a); break;
+          case kScanBF16: compare_class<kScanBF16>(d, flat, s, e, a); break;
+          case kCmpRaw1: compare_class<kCmpRaw1>(d, flat, s, e, a); break;
+          case kCmpRaw2: compare_class<kCmpRaw2>(d, flat, s, e, a); break;
+          case kCmpRaw4: compare_class<kCmpRaw4>(d, flat, s, e, a); break;
+          case kCmpRaw8: compare_class<kCmpRaw8>(d, flat, s, e, a); break;
+          case kCmpRaw16: compare_class<kCmpRaw16>(d, flat, s, e, a); break;
+          case kCmpBF16toF32:
+            compare_class<kCmpBF16toF32>(d, flat, s, e, a);
+            break;
+          default: compare_class<kCmpF16toF32>(d, flat, s, e, a); break;
+        }
+        n_diff += a.n_diff;
+        n_nonfinite += a.n_nonfinite;
+        kmax = a.kmax;
+        // the owner, and so the path to here, is uniform across the
+        // workgroup: every thread reaches both barriers
+        store_unit_sums(wave_sums, partials,
+                        wu_prefix[owner] + s / kWorkUnitBytes, a.sq, a.ref);
+      });
+  if (cur >= 0) flush();
+}
+
+// Stage two of words 4-5: one wave per descriptor.
+__global__ __launch_bounds__(64) void compare_finish_kernel(
+    int n, const unsigned long long* __restrict__ wu_prefix,
+    const double* __restrict__ partials, unsigned long long* __restrict__ out) {
+  const int i = blockIdx.x;
+  if (i >= n) return;
+  double sq, ref;
+  finish_unit_sums(partials, wu_prefix[i], wu_prefix[i + 1], sq, ref);
+  if (threadIdx.x == 0) {
+    out[6 * i + 4] = (unsigned long long)__double_as_longlong(sq);
+    out[6 * i + 5] = (unsigned long long)__double_as_longlong(ref);
   }
 }
 
@@ -1323,6 +1679,59 @@ std::string env_or_empty(const char* name) {
   return v ? std::string(v) : std::string();
 }
 
+// Bring `tables` to the device and call enqueue_kernel(device copy) behind
+// the upload on `stream`: through a slot of `ring` (nothing waits for the
+// stream), or, for a table larger than a slot, through an allocation of its
+// own and a copy that does wait.
+template <typename Enqueue>
+void enqueue_with_tables(HipTableRing& ring, hipStream_t stream,
+                         const LaunchTables& tables, Enqueue enqueue_kernel) {
+  const size_t table_bytes = tables.host.size();
+  const size_t slot_bytes = ring.policy.slot_bytes();
+  const bool ringed = ring.policy.launch(
+      table_bytes,
+      [&](int slot) { HIP_CHECK(hipEventSynchronize(ring.ev[slot])); },
+      [&](int slot) {
+        char* h_tables = ring.host + slot * slot_bytes;
+        char* d_tables = ring.dev + slot * slot_bytes;
+        std::memcpy(h_tables, tables.host.data(), table_bytes);
+        try {
+          // out of pinned memory: enqueued, not waited for
+          HIP_CHECK(hipMemcpyAsync(d_tables, h_tables, table_bytes,
+                                   hipMemcpyHostToDevice, stream));
+          enqueue_kernel(d_tables);
+          HIP_CHECK(hipEventRecord(ring.ev[slot], stream));
+        } catch (...) {
+          // the slot goes back unrecorded: nothing may still read it
+          (void)hipStreamSynchronize(stream);
+          throw;
+        }
+      });
+  if (!ringed) {
+    // A table larger than a slot (a slab of hundreds of members): a device
+    // allocation of its own and a copy out of pageable memory, which waits
+    // for the stream. The synchronise makes that explicit, so the host
+    // image may go out of scope whatever the runtime did with it.
+    void* scratch = nullptr;
+    HIP_CHECK(hipMallocAsync(&scratch, table_bytes, stream));
+    hipError_t err = hipMemcpyAsync(scratch, tables.host.data(), table_bytes,
+                                    hipMemcpyHostToDevice, stream);
+    const hipError_t sync_err = hipStreamSynchronize(stream);
+    if (err == hipSuccess) err = sync_err;
+    if (err == hipSuccess) {
+      try {
+        enqueue_kernel(scratch);
+      } catch (...) {
+        (void)hipFreeAsync(scratch, stream);
+        throw;
+      }
+    }
+    const hipError_t free_err = hipFreeAsync(scratch, stream);
+    if (err == hipSuccess) err = free_err;
+    HIP_CHECK(err);
+  }
+}
+
 // One launcher for the three copy entry points. `kind` picks the rules
 // check_descs applies and the kernel family: Gather runs pack_kernel on
 // the D2H side stream, Scatter and Unpack run unpack_kernel on the H2D
@@ -1383,7 +1792,6 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
 
   // descriptors + prefix sums: one host image, one copy
   const LaunchTables tables(descs, wu_prefix);
-  const size_t table_bytes = tables.host.size();
 
   // everything that follows the table upload on the stream, up to and
   // including the kernel that reads the tables at `d_tables`
@@ -1416,50 +1824,8 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
     HIP_CHECK(hipGetLastError());
   };
 
-  HipTableRing& ring = gather ? ctx.d2h_ring : ctx.h2d_ring;
-  const size_t slot_bytes = ring.policy.slot_bytes();
-  const bool ringed = ring.policy.launch(
-      table_bytes,
-      [&](int slot) { HIP_CHECK(hipEventSynchronize(ring.ev[slot])); },
-      [&](int slot) {
-        char* h_tables = ring.host + slot * slot_bytes;
-        char* d_tables = ring.dev + slot * slot_bytes;
-        std::memcpy(h_tables, tables.host.data(), table_bytes);
-        try {
-          // out of pinned memory: enqueued, not waited for
-          HIP_CHECK(hipMemcpyAsync(d_tables, h_tables, table_bytes,
-                                   hipMemcpyHostToDevice, stream));
-          enqueue_kernel(d_tables);
-          HIP_CHECK(hipEventRecord(ring.ev[slot], stream));
-        } catch (...) {
-          // the slot goes back unrecorded: nothing may still read it
-          (void)hipStreamSynchronize(stream);
-          throw;
-        }
-      });
-  if (!ringed) {
-    // A table larger than a slot (a slab of hundreds of members): a device
-    // allocation of its own and a copy out of pageable memory, which waits
-    // for the stream. The synchronise makes that explicit, so the host
-    // image may go out of scope whatever the runtime did with it.
-    void* scratch = nullptr;
-    HIP_CHECK(hipMallocAsync(&scratch, table_bytes, stream));
-    hipError_t err = hipMemcpyAsync(scratch, tables.host.data(), table_bytes,
-                                    hipMemcpyHostToDevice, stream);
-    const hipError_t sync_err = hipStreamSynchronize(stream);
-    if (err == hipSuccess) err = sync_err;
-    if (err == hipSuccess) {
-      try {
-        enqueue_kernel(scratch);
-      } catch (...) {
-        (void)hipFreeAsync(scratch, stream);
-        throw;
-      }
-    }
-    const hipError_t free_err = hipFreeAsync(scratch, stream);
-    if (err == hipSuccess) err = free_err;
-    HIP_CHECK(err);
-  }
+  enqueue_with_tables(gather ? ctx.d2h_ring : ctx.h2d_ring, stream, tables,
+                      enqueue_kernel);
 
   if (gather && slab_ptr != 0) {
     // slab mode: one SDMA copy moves the packed slab to pinned host memory
@@ -1832,6 +2198,107 @@ static std::vector<unsigned long long> tensor_stats(
       &init, (size_t)total_wus * 2 * sizeof(double));
 }
 
+// ---------------------------------------------------------------------------
+// a stored payload against N live strided device tensors (blocking): one
+// launch of compare_kernel and one of compare_finish_kernel for all the
+// members of one read. `flat` holds unpack-style descriptor rows (flat_off
+// inside the payload, cast codes 0, 3, 4), `classes` one kCmp* code per
+// descriptor; the payload is `total_bytes` at `flat_ptr`: pinned host
+// memory, read in place over PCIe, when `flat_on_host`, else device memory.
+// Runs on the H2D side stream behind the producer's, tables through that
+// stream's ring like a restore scatter. Returns 6*n words (see
+// compare_kernel), word 0 filled in here.
+// ---------------------------------------------------------------------------
+
+static std::vector<unsigned long long> compare_tensors(
+    const std::vector<unsigned long long>& flat, int n,
+    const std::vector<uint32_t>& classes, uintptr_t flat_ptr,
+    bool flat_on_host, unsigned long long total_bytes,
+    uintptr_t producer_stream, int device) {
+  // refused before the GPU is touched
+  const std::vector<Desc> descs = parse_descs(flat, n);
+  const FlatSide flat_side{0, flat_ptr, total_bytes, 0};
+  check_descs(descs, DescKind::Compare, &flat_side, &classes);
+
+  std::vector<unsigned long long> results(6 * (size_t)n, 0);
+  for (size_t i = 0; i < (size_t)n; ++i) {
+    results[6 * i] = descs[i].nbytes / cmp_elem_size(classes[i]);
+  }
+  const std::vector<unsigned long long> wu_prefix = wu_prefix_of(descs);
+  const unsigned long long total_wus = wu_prefix[n];
+  if (total_wus == 0) return results;
+
+  // descriptors | prefix sums | classes
+  const LaunchTables tables(descs, wu_prefix, classes.data(),
+                            sizeof(uint32_t) * n);
+  // Out of pinned memory the kernel is PCIe-bound like the direct restore
+  // scatter, and 256 workgroups reach the link rate; out of HBM it is the
+  // stats kernel's read with f64 work behind it
+  const unsigned int grid = grid_for(total_wus, flat_on_host ? 256ull : 2048ull,
+                                     getenv("TSAMD_PACK_GRID"));
+  const size_t result_bytes = sizeof(unsigned long long) * results.size();
+  const size_t partial_bytes = (size_t)total_wus * 2 * sizeof(double);
+
+  py::gil_scoped_release release;
+  HIP_CHECK(hipSetDevice(device));
+  DeviceCtx& ctx = get_ctx(device);
+  hipStream_t stream = ctx.h2d_stream;
+  const char* flat_base = reinterpret_cast<const char*>(flat_ptr);
+  if (flat_on_host) {
+    void* dev_ptr = nullptr;
+    if (hipHostGetDevicePointer(&dev_ptr, reinterpret_cast<void*>(flat_ptr),
+                                0) == hipSuccess &&
+        dev_ptr != nullptr) {
+      flat_base = static_cast<const char*>(dev_ptr);
+    }
+  }
+  chain_after(stream, producer_stream, device);
+
+  // results, then the partial sums of stage one, in one allocation
+  void* scratch = nullptr;
+  HIP_CHECK(hipMallocAsync(&scratch, result_bytes + partial_bytes, stream));
+  unsigned long long* d_out = static_cast<unsigned long long*>(scratch);
+  double* d_partials = reinterpret_cast<double*>(d_out + results.size());
+  hipError_t err = hipMemsetAsync(d_out, 0, result_bytes, stream);
+  std::string refusal;
+  if (err == hipSuccess) {
+    try {
+      enqueue_with_tables(ctx.h2d_ring, stream, tables, [&](const void* d_tables) {
+        hipLaunchKernelGGL(
+            compare_kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
+            tables.descs(d_tables),
+            static_cast<const uint32_t*>(tables.extra(d_tables)), n,
+            tables.prefix(d_tables), total_wus, flat_base, d_out, d_partials);
+        hipLaunchKernelGGL(compare_finish_kernel, dim3((unsigned int)n),
+                           dim3(64), 0, stream, n, tables.prefix(d_tables),
+                           static_cast<const double*>(d_partials), d_out);
+        HIP_CHECK(hipGetLastError());
+      });
+    } catch (const std::exception& e) {
+      refusal = e.what();
+    }
+  }
+  // words 1-5 come back; word 0 is the host's. Whatever happened, the
+  // stream is drained before `results` and the scratch go away
+  std::vector<unsigned long long> got(results.size(), 0);
+  if (err == hipSuccess && refusal.empty()) {
+    err = hipMemcpyAsync(got.data(), d_out, result_bytes,
+                         hipMemcpyDeviceToHost, stream);
+  }
+  (void)hipFreeAsync(scratch, stream);
+  const hipError_t sync_err = hipStreamSynchronize(stream);
+  if (!refusal.empty()) throw std::runtime_error("compare_tensors: " + refusal);
+  if (err == hipSuccess) err = sync_err;
+  if (err != hipSuccess) {
+    throw std::runtime_error(std::string("compare_tensors: ") +
+                             hipGetErrorString(err));
+  }
+  for (size_t i = 0; i < got.size(); ++i) {
+    if (i % 6 != 0) results[i] = got[i];
+  }
+  return results;
+}
+
 // Host-side psum64 (single pass, std::thread-parallel): the
 // python-level vectorized implementations burn ~10 full memory passes
 // on splitmix temporaries (~0.2-0.3 GB/s); this one runs at memcpy-ish
@@ -2053,6 +2520,15 @@ PYBIND11_MODULE(_csnap, m) {
         "bits; max_grid > 0 bounds the workgroups",
         py::arg("flat"), py::arg("n"), py::arg("classes"), py::arg("device"),
         py::arg("stream"), py::arg("max_grid") = 0);
+  m.def("compare_tensors", &compare_tensors,
+        "compare a stored payload, read in place from pinned host memory "
+        "(flat_on_host) or from device memory, with live strided device "
+        "tensors (blocking); six words per descriptor: n, n_diff, "
+        "n_nonfinite_diff, and max |v - s|, sum (v - s)^2, sum s^2 as f64 "
+        "bits over the pairs with both sides finite",
+        py::arg("flat"), py::arg("n"), py::arg("classes"),
+        py::arg("flat_ptr"), py::arg("flat_on_host"), py::arg("total_bytes"),
+        py::arg("stream"), py::arg("device"));
   m.def("file_write", &::file_write,  // not tsamd::file_write
        
         "write a buffer to a file (GIL released); reuse=True overwrites an "

@@ -823,6 +823,136 @@ def host_tensor_stats(
     return torch_tensor_stats(t.detach().cpu(), stored_dtype)
 
 
+# ---------------------------------------------------------------------------
+# compare: descriptors, the six fields, the torch expression
+# ---------------------------------------------------------------------------
+
+# Six fields per tensor, stored payload s against live tensor v
+# (compare_kernel in ops/hip/staging.hip): [n, n_diff, n_nonfinite_diff,
+# max_abs, sum_sq, ref_sum_sq]. The last three are floats over the pairs with
+# both sides finite, and None for dtypes that are compared bitwise only.
+# Element classes (kCmp* in ops/hip/desc_check.h): the stats classes for
+# equal float dtypes, raw by element size, and the two widen pairs.
+_CMP_RAW_CLASSES = {1: 4, 2: 5, 4: 6, 8: 7, 16: 8}
+_CMP_WIDEN_CLASSES = {CAST_BF16_TO_F32: 9, CAST_F16_TO_F32: 10}
+_CMP_FIRST_RAW, _CMP_LAST_RAW = 4, 8
+
+Member = Tuple[torch.Tensor, torch.dtype, int]  # live view, stored dtype, flat offset
+
+
+def compare_class(live: torch.Tensor, stored_dtype: torch.dtype) -> Optional[int]:
+    """The compare kernel's element class for a ``stored_dtype`` payload
+    against ``live``, or None when the kernel must not be used and the
+    caller takes torch_tensor_diff(). It declines what scatter_plan()
+    declines, for the same reasons, except internal overlap of the tensor:
+    nothing is written, and an element that is visited twice is compared
+    twice, as torch does."""
+    if (
+        live.device.type != "cuda"
+        or live.layout != torch.strided
+        or live.is_quantized
+        or live.is_conj()
+        or live.is_neg()
+    ):
+        return None
+    if stored_dtype != live.dtype:
+        cls = _CMP_WIDEN_CLASSES.get(_WIDEN_CODES.get((stored_dtype, live.dtype)))
+    else:
+        cls = _STATS_CLASSES.get(live.dtype, _CMP_RAW_CLASSES.get(live.element_size()))
+    if (
+        cls is None
+        or outer_dim_count(live) > MAX_OUTER_DIMS
+        or live.numel() * stored_dtype.itemsize >= _KERNEL_MAX_BYTES
+        or live.data_ptr() % live.element_size()
+    ):
+        return None
+    return cls
+
+
+def build_compare_items(
+    members: Sequence[Member], flat_base: int = 0
+) -> Tuple[List[Optional[PackItem]], List[Optional[int]]]:
+    """Compare-kernel descriptors and classes for the members of one read,
+    one entry each: the scatter's descriptors (``vec`` divides the flat
+    address ``flat_base + offset`` too). Both entries are None for a member
+    the kernel declines: see compare_class(), or a payload address that
+    splits a stored element."""
+    items: List[Optional[PackItem]] = []
+    classes: List[Optional[int]] = []
+    for live, stored, off in members:
+        cls = compare_class(live, stored)
+        item = None
+        if cls is not None and (flat_base + off) % stored.itemsize == 0:
+            (item,) = build_scatter_items([live], [stored], [off], flat_base)
+            if item.nbytes and item.vec < stored.itemsize:
+                item = None
+        items.append(item)
+        classes.append(cls if item is not None else None)
+    return items, classes
+
+
+def decode_diff(words: Sequence[int], cls: int) -> List[Any]:
+    """The six fields of the kernel's six words for a descriptor of class
+    ``cls``."""
+    if _CMP_FIRST_RAW <= cls <= _CMP_LAST_RAW:
+        return [words[0], words[1], 0, None, None, None]
+    return list(words[:3]) + [_f64_of(w) for w in words[3:6]]
+
+
+def torch_tensor_diff(stored: torch.Tensor, live: torch.Tensor) -> List[Any]:
+    """The six fields by torch expressions in float64, on ``live``'s device:
+    what the compare kernel must agree with (exactly but for the two sums,
+    which agree to rounding), and the path for host tensors and for
+    everything the kernel declines. ``stored`` has ``live``'s shape; it is
+    brought to ``live``'s dtype first, and quantized tensors are compared
+    dequantized."""
+    live = resolve_lazy(live.detach())
+    stored = resolve_lazy(stored.detach()).to(live.device)
+    if live.layout != torch.strided:
+        live = live.to_dense()
+    if stored.layout != torch.strided:
+        stored = stored.to_dense()
+    if live.is_quantized:
+        live = live.dequantize()
+    if stored.is_quantized:
+        stored = stored.dequantize()
+    stored = stored.to(live.dtype)
+    n = live.numel()
+    if n == 0:
+        zero = 0.0 if live.dtype in _STATS_CLASSES else None
+        return [0, 0, 0, zero, zero, zero]
+    esz = live.element_size()
+    s_bytes = stored.contiguous().reshape(-1).view(torch.uint8).reshape(n, esz)
+    v_bytes = live.contiguous().reshape(-1).view(torch.uint8).reshape(n, esz)
+    differ = (s_bytes != v_bytes).any(dim=1)
+    n_diff = int(differ.sum())
+    if live.dtype not in _STATS_CLASSES:
+        return [n, n_diff, 0, None, None, None]
+    s = stored.reshape(-1).to(torch.float64)
+    v = live.reshape(-1).to(torch.float64)
+    both = torch.isfinite(s) & torch.isfinite(v)
+    d = (v - s)[both]
+    ref = s[both]
+    return [
+        n,
+        n_diff,
+        int((differ & ~both).sum()),
+        float(d.abs().max()) if d.numel() else 0.0,
+        float((d * d).sum()),
+        float((ref * ref).sum()),
+    ]
+
+
+def merge_diff(a: Sequence[Any], b: Sequence[Any]) -> List[Any]:
+    """The six fields of two disjoint sets of pairs taken together: counters
+    add, the maximum is the larger, the sums add as float64, ``a`` first.
+    A numeric field is None when it is None on either side."""
+    out: List[Any] = [a[0] + b[0], a[1] + b[1], a[2] + b[2]]
+    for i, op in ((3, max), (4, float.__add__), (5, float.__add__)):
+        out.append(None if a[i] is None or b[i] is None else op(a[i], b[i]))
+    return out
+
+
 def _items_to_flat(items: List[PackItem]) -> List[int]:
     """Serialize descriptors for the extension: fixed-width int rows."""
     flat: List[int] = []
@@ -1417,6 +1547,59 @@ class StagingEngine:
             empty=STATS_EMPTY,
         )
         return [list(row) for row in zip(*columns)] if tensors else []
+
+    # -- compare ------------------------------------------------------------
+
+    def compare(
+        self,
+        flat: Any,
+        nbytes: int,
+        members: Sequence[Member],
+    ) -> List[List[Any]]:
+        """The six fields (torch_tensor_diff) of each member of one read:
+        the first ``nbytes`` of ``flat`` against live tensors of this
+        device, from ONE launch of the compare kernel (and its finish
+        launch) over all eligible members. ``flat`` is the PinnedBlock the
+        read landed in, which the kernel reads in place over PCIe, or a
+        uint8 device tensor. ``members`` holds ``(live view, stored dtype,
+        flat offset)`` triples. Nothing is written to either side, and no
+        payload-sized device memory is allocated. Blocking.
+
+        Members build_compare_items() declines are compared with the torch
+        expression instead; so is everything when the extension is disabled
+        by TSAMD_DISABLE_HIP_STAGING=1."""
+        on_host = isinstance(flat, PinnedBlock)
+        flat_u8 = flat.tensor if on_host else flat
+        if self._use_ext:
+            items, classes = build_compare_items(members, flat_u8.data_ptr())
+        else:
+            items = classes = [None] * len(members)
+        out: List[Any] = [None] * len(members)
+        taken = [i for i, it in enumerate(items) if it is not None]
+        if taken:
+            dev_index = self.device.index or 0
+            with torch.cuda.device(dev_index):
+                got = _csnap.compare_tensors(
+                    _items_to_flat([items[i] for i in taken]),
+                    len(taken),
+                    [classes[i] for i in taken],
+                    flat_u8.data_ptr(),
+                    on_host,
+                    nbytes,
+                    torch.cuda.current_stream().cuda_stream,
+                    dev_index,
+                )
+            for k, i in enumerate(taken):
+                out[i] = decode_diff(got[6 * k : 6 * k + 6], classes[i])
+        for i, (live, stored, off) in enumerate(members):
+            if out[i] is None:
+                piece = flat_u8[off : off + live.numel() * stored.itemsize]
+                if (flat_u8.storage_offset() + off) % stored.itemsize:
+                    piece = piece.clone()  # a view needs whole elements
+                out[i] = torch_tensor_diff(
+                    piece.view(stored).reshape(live.shape), live
+                )
+        return out
 
     # -- what the read-only launches share -----------------------------------
 

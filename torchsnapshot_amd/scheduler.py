@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import asyncio
 import logging
+import os
 import socket
 import threading
 import time
@@ -60,15 +61,21 @@ def get_local_world_size(pg: PGWrapper) -> int:
     return hostnames.count(socket.gethostname())
 
 
-def get_process_memory_budget_bytes(pg: PGWrapper) -> int:
+def get_process_memory_budget_bytes(pg: PGWrapper, collective: bool = True) -> int:
+    """``collective=False`` is for entry points a rank may call alone
+    (Snapshot.compare): the ranks on this host are then the launcher's
+    LOCAL_WORLD_SIZE, or, without one, the whole world (the smaller
+    budget), and nothing is gathered."""
     override = knobs.get_memory_budget_override_bytes()
     if override is not None:
         logger.info("Manual memory budget: %d bytes", override)
         return override
     available = psutil.virtual_memory().available
-    budget = int(
-        available * _AVAILABLE_MEMORY_FRACTION / max(get_local_world_size(pg), 1)
-    )
+    if collective:
+        local = get_local_world_size(pg)
+    else:
+        local = int(os.environ.get("LOCAL_WORLD_SIZE") or pg.get_world_size())
+    budget = int(available * _AVAILABLE_MEMORY_FRACTION / max(local, 1))
     return min(budget, _MAX_PER_RANK_MEMORY_BUDGET_BYTES)
 
 

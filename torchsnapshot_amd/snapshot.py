@@ -4,6 +4,8 @@
     Snapshot.async_take(path, app_state)    — non-blocking save (training
                                               resumes once staging is done)
     Snapshot(path).restore(app_state)       — in-place load
+    Snapshot(path).compare(app_state)       — element-wise diff against live
+                                              state, nothing written
     Snapshot(path).read_object(path)        — random access to one object
     Snapshot(path).get_manifest()           — inspection
 
@@ -33,6 +35,7 @@ import torch
 import torch.distributed as dist
 
 from . import (
+    compare as _compare,
     knobs,
     nonfinite as _nonfinite,
     replication as _replication,
@@ -41,7 +44,12 @@ from . import (
 from .dist_store import LinearBarrier, get_or_create_store
 from .event import Event, log_event
 from .flatten import Flattened, flatten, inflate
-from .io_preparer import prepare_read, prepare_write
+from .io_preparer import (
+    _is_dtensor,
+    _is_sharded_tensor,
+    prepare_read,
+    prepare_write,
+)
 from .io_preparers.dtensor import planning_memo
 from .io_types import ReadReq, StoragePlugin, WriteIO, WriteReq
 from .manifest import (
@@ -51,6 +59,7 @@ from .manifest import (
     METADATA_FILENAME,
     PrimitiveEntry,
     SnapshotMetadata,
+    TensorEntry,
 )
 from .manifest_ops import (
     get_manifest_for_rank,
@@ -961,6 +970,105 @@ class Snapshot:
             except TypeError:
                 pass  # stateful doesn't accept strict
         stateful.load_state_dict(state_dict_to_load)
+
+    # -- compare --------------------------------------------------------------
+
+    def compare(self, app_state: AppState) -> Dict[str, "_compare.TensorDiff"]:
+        """Compare this snapshot with the live ``app_state``, element by
+        element: ``{logical path: TensorDiff}`` with one entry per tensor
+        leaf on this rank. It shares restore's planning (the manifest for
+        this rank, resharding, replicated entries, the memory budget) and
+        its read pipeline, with the consumers comparing where they would
+        write: device tensors by the compare kernel straight out of pinned
+        memory. ``app_state`` is not modified and nothing under the snapshot
+        path is touched; there are no collectives, and a sharded leaf covers
+        this rank's elements only. Leaves on one side only and leaves whose
+        shapes differ come back with a ``note`` and ``n == 0``; non-tensor
+        leaves are skipped. Blocks until the result is complete."""
+        torch._C._log_api_usage_once("torchsnapshot_amd.Snapshot.compare")
+        self._validate_app_state(app_state)
+        pg_wrapper = PGWrapper(self.pg)
+        rank = pg_wrapper.get_rank()
+        event_meta = {"id": uuid.uuid4().hex, "rank": rank, "api": "compare"}
+        log_event(Event("compare_start", dict(event_meta)))
+        try:
+            storage = url_to_storage_plugin(self.path, self._storage_options)
+            try:
+                metadata = self.metadata
+                _, payload_entries = get_manifest_for_rank(metadata, rank)
+                from . import integrity
+
+                checksums = (
+                    integrity.load_checksums(storage, metadata.world_size)
+                    if integrity.verification_enabled()
+                    else None
+                )
+                sink = _compare.CompareSink()
+                read_reqs: List[ReadReq] = []
+                for key in sorted(app_state):
+                    read_reqs += self._plan_compare(
+                        key, app_state[key], payload_entries, sink
+                    )
+                sync_execute_read_reqs(
+                    _batch_reads(read_reqs),
+                    storage,
+                    get_process_memory_budget_bytes(pg_wrapper, collective=False),
+                    rank=rank,
+                    checksums=checksums,
+                )
+            finally:
+                storage.sync_close()
+            log_event(Event("compare_end", {**event_meta, "success": True}))
+            return sink.result()
+        except Exception:
+            log_event(Event("compare_end", {**event_meta, "success": False}))
+            raise
+
+    @staticmethod
+    def _plan_compare(
+        key: str,
+        stateful: Stateful,
+        payload_entries: Dict[str, Entry],
+        sink: "_compare.CompareSink",
+    ) -> List[ReadReq]:
+        """The reads of one stateful's tensor leaves, each consumer with the
+        compare action; what cannot be compared becomes a note."""
+        _, live = flatten(stateful.state_dict(), prefix=key)
+        prefix = f"{key}/"
+        stored = {
+            p: e
+            for p, e in payload_entries.items()
+            if (p == key or p.startswith(prefix)) and hasattr(e, "shape")
+        }
+        read_reqs: List[ReadReq] = []
+        for p, obj in live.items():
+            entry = stored.get(p)
+            distributed = _is_sharded_tensor(obj) or _is_dtensor(obj)
+            if not isinstance(obj, torch.Tensor) and not distributed:
+                if entry is not None:
+                    sink.note(p, "not a tensor in app_state")
+                continue
+            if entry is None:
+                sink.note(p, "missing in snapshot")
+                continue
+            plain_entry = isinstance(entry, (TensorEntry, ChunkedTensorEntry))
+            if distributed and plain_entry:
+                sink.note(p, "sharded in app_state, one tensor in snapshot")
+                continue
+            shape = (
+                obj.metadata().size if _is_sharded_tensor(obj) else obj.shape
+            )
+            # a sharded entry may have been recorded without its global shape
+            if (plain_entry or entry.shape) and list(shape) != list(entry.shape):
+                sink.note(p, f"shape {tuple(entry.shape)} vs {tuple(shape)}")
+                continue
+            reqs, _ = prepare_read(entry, obj)
+            _compare.attach_compare(reqs, sink, p, entry)
+            read_reqs += reqs
+        for p in stored:
+            if p not in live:
+                sink.note(p, "missing in app_state")
+        return read_reqs
 
     def get_state_dict_for_key(self, key: str) -> Dict[str, Any]:
         """Load and return the state dict saved for ``key`` without an
