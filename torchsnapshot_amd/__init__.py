@@ -15,6 +15,7 @@ from .rng_state import RNGState
 from .snapshot import PendingSnapshot, Snapshot
 from .state_dict import StateDict
 from .stateful import AppState, Stateful
+from .tensor_hist import TensorHistogram, tensor_histograms
 from .tensor_stats import TensorStats, tensor_stats
 from .version import __version__
 
@@ -31,6 +32,8 @@ __all__ = [
     "fingerprint_state",
     "TensorStats",
     "tensor_stats",
+    "TensorHistogram",
+    "tensor_histograms",
     "TensorDiff",
     "__version__",
 ]

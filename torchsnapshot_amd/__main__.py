@@ -4,6 +4,8 @@
     python -m torchsnapshot_amd cat <path> <entry>   # print one object
     python -m torchsnapshot_amd stats <path> [--against <other>]
                                                      # recorded statistics
+    python -m torchsnapshot_amd hist <path> [<glob>] [--narrow <dtype>]
+                                                     # exponent histograms
     python -m torchsnapshot_amd compare <path> <other>
                                                      # element-wise difference
 """
@@ -157,6 +159,37 @@ def cmd_compare(args: argparse.Namespace) -> int:
     return 1 if rows else 0
 
 
+_NARROW = ("float16", "bfloat16", "float8_e4m3fn", "float8_e5m2")
+
+
+def cmd_hist(args: argparse.Namespace) -> int:
+    import fnmatch
+
+    import torch
+
+    hists = Snapshot(args.path).get_histograms()
+    if not hists:
+        print(f"{args.path}: no histograms recorded (take(..., histogram=True))")
+        return 1
+    for path, h in hists.items():
+        if args.glob is not None and not fnmatch.fnmatchcase(path, args.glob):
+            continue
+        lo, hi = h.exponent_range
+        span = f"2^{lo}..2^{hi}" if h.bins else "-"
+        line = (
+            f"{path}: n={h.n} exponents={span} n_zero={h.n_zero} "
+            f"n_negative={h.n_negative} n_nonfinite={h.n_nonfinite}"
+        )
+        if args.narrow is not None:
+            over, flushed, sub = h.narrowing(getattr(torch, args.narrow))
+            line += (
+                f" {args.narrow}: overflow={over} flushed={flushed} "
+                f"subnormal={sub}"
+            )
+        print(line)
+    return 0
+
+
 def main(argv=None) -> int:
     parser = argparse.ArgumentParser(prog="python -m torchsnapshot_amd")
     sub = parser.add_subparsers(dest="cmd", required=True)
@@ -185,6 +218,20 @@ def main(argv=None) -> int:
     p_compare.add_argument("path")
     p_compare.add_argument("other")
     p_compare.set_defaults(fn=cmd_compare)
+    p_hist = sub.add_parser(
+        "hist",
+        help="print the exponent histograms recorded by take(..., histogram=True)",
+    )
+    p_hist.add_argument("path")
+    p_hist.add_argument("glob", nargs="?", help="only leaves matching this glob")
+    p_hist.add_argument(
+        "--narrow",
+        metavar="DTYPE",
+        choices=sorted(_NARROW),
+        help="also print how many elements a cast to DTYPE would turn into "
+        "Inf, flush to zero or leave subnormal, by binade",
+    )
+    p_hist.set_defaults(fn=cmd_hist)
     args = parser.parse_args(argv)
     return args.fn(args)
 

@@ -18,6 +18,9 @@
 //   - stats kernel: count, zeros, min, max, sum and sum of squares of each
 //     tensor's finite elements in f64, read in place over the same
 //     descriptors, with sums that are bit-identical for any grid (stats=)
+//   - histogram kernel: the distribution of floor(log2|x|) of each tensor
+//     over the same descriptors, binned in 32 private LDS copies of 280
+//     counters per workgroup (histogram=)
 //   - compare kernel: a stored payload, read in place from pinned host
 //     memory or from HBM, against the live strided tensors element by
 //     element; both sides read-only, six words per tensor, the f64 sums
@@ -44,7 +47,7 @@
 //     descriptor before the GPU is touched; wu_prefix_of, grid_for and
 //     LaunchTables are the launch prologue of both launchers: launch_pack
 //     for the copies, read_launch for the blocking read-only scan,
-//     fingerprint and statistics
+//     fingerprint, statistics and histogram
 //   - on the host (table_ring.h): the launch tables reach the device
 //     through a ring of pinned slots, so a launch never waits for the
 //     stream it enqueues on, and the launch entry points hold no GIL
@@ -1230,6 +1233,252 @@ __global__ __launch_bounds__(64) void stats_finish_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// exponent histogram: kHistWords u64 words per descriptor, read in place and
+// read-only over the stats kernel's descriptors and classes (f64, f32, f16,
+// bf16):
+//
+//   0      n_zero: +0 and -0
+//   1      n_negative: finite, non-zero, sign bit set
+//   2      n_nonfinite: NaN and +-Inf
+//   3 + k  finite non-zero elements with floor(log2|x|) == k - 149,
+//          k = 0..276: every f32 binade, subnormal ones included, which
+//          covers f16 and bf16; an f64 element outside lands in the end bin
+//
+// so that words[0] + words[2] + sum(words[3:]) is the element count.
+//
+//   - classification is integer arithmetic on the bit patterns: a normal
+//     element's bin is its exponent field plus a constant, a subnormal's the
+//     position of its leading mantissa bit (one clz). Zero and non-finite are
+//     two selects on the same masked value, so every element ends as ONE word
+//     index and one counter increment; nothing depends on the float mode
+//   - the counters live in LDS, u32, in kHistCopies = 32 private copies per
+//     workgroup; a lane counts in copy (lane & 31). Trained weights sit in a
+//     few adjacent binades, so with one copy most of a wave's 64 lanes would
+//     meet on one address in one instruction and the LDS would take them one
+//     after the other; with 32 copies at most the two lanes l and l + 32 of a
+//     wave can, whatever the data
+//   - layout: word-major, copies interleaved, counter (w, c) at
+//     bins[w * 32 + c]. The bank of an LDS dword is its index modulo the
+//     number of banks, so with 32 banks a lane's bank is (w * 32 + c) % 32 =
+//     lane & 31 for EVERY word w: the 32 lanes of a half wave always fall in
+//     32 different banks, and bin values cannot make them collide. (With 64
+//     banks the bank is 32 * (w & 1) + c, still distinct within a half wave.)
+//     The copy-major layout bins[c * 280 + w] has no such property: 280 = 8
+//     mod 32, so for one shared bin the copies c and c + 4 share a bank, an
+//     8-way conflict on exactly the hostile input; a padded stride of 281
+//     fixes one shared bin but not neighbouring bins (copy c, bin w + 1 meets
+//     copy c + 1, bin w)
+//   - size: 280 * 32 * 4 = 35840 bytes per workgroup, so 4 workgroups (16
+//     waves, 4 per SIMD) fit the 160 KiB of a CU. 64 copies would leave 2
+//     workgroups, too few waves to cover HBM latency, for a gain only where
+//     lanes l and l + 32 are issued together; 16 copies would double the
+//     lanes per address. With 32 the kernel's time does not depend on the
+//     values at all, against 5.4x between the friendliest and the most
+//     hostile input with one copy (profiles/tensor_hist_measurements.md)
+//   - n_negative is not a second LDS increment per element (half of all
+//     elements are negative): a lane keeps it in a register and adds it to
+//     word 1 of its own copy when the counters are flushed
+//   - the counters are carried from one work unit to the next while the
+//     workgroup stays on one descriptor. When the owner changes, and at the
+//     end: barrier; thread t sums word t, t + 256, ... over the 32 copies,
+//     clears what it read, and adds a non-zero total to out[280 * owner + w]
+//     with one u64 atomic; barrier. The owner is a function of blockIdx and
+//     the tables alone, so it is uniform across the workgroup and so is every
+//     path to a barrier
+//   - a u32 counter cannot wrap: check_descs keeps a descriptor under 4 GiB,
+//     an element has at least 2 bytes, so one descriptor has fewer than 2^31
+//     elements, and the counters are flushed per descriptor at the latest.
+//     The same bound holds for a lane's n_negative register
+//   - every word is an integer count added with integer atomics: any grid,
+//     any batch order and any max_grid give the same bits
+// ---------------------------------------------------------------------------
+
+constexpr uint32_t kHistWords = 280;
+constexpr uint32_t kHistBins = kHistWords - 3;  // k = 0..276
+constexpr uint32_t kHistCopies = 32;
+
+// what one lane keeps: its copy of the counters (word w at mine[w * 32]) and
+// its negative elements since the last flush
+struct HistLane {
+  uint32_t* mine;
+  uint32_t n_negative;
+};
+
+// One element, as its pattern without the sign (`a`), the first non-finite
+// pattern of its format and its word among the bins.
+__device__ __forceinline__ void hist_elem(uint32_t a, uint32_t sign,
+                                          uint32_t first_nonfinite,
+                                          uint32_t bin_word, HistLane& h) {
+  const bool finite = a < first_nonfinite;
+  uint32_t w = finite ? bin_word : 2u;
+  w = a == 0u ? 0u : w;
+  h.n_negative += sign & (uint32_t)(finite & (a != 0u));
+  atomicAdd(&h.mine[w * kHistCopies], 1u);  // ds_add_u32, no return value
+}
+
+// f32 pattern: exponent field E != 0 is binade E - 127, word 3 + E + 22; a
+// subnormal m * 2^-149 with its leading bit at position p = 31 - clz(m) is
+// binade p - 149, word 3 + p. (__clz(0) is 32; zero is selected away.)
+__device__ __forceinline__ void hist_f32(uint32_t u, HistLane& h) {
+  const uint32_t a = u & 0x7FFFFFFFu;
+  const uint32_t exp = a >> 23;
+  const uint32_t word = exp != 0u ? exp + 25u : 34u - (uint32_t)__clz((int)a);
+  hist_elem(a, u >> 31, 0x7F800000u, word, h);
+}
+
+// f16 pattern: E != 0 is binade E - 15, word 3 + E + 134; a subnormal
+// m * 2^-24 is binade p - 24, word 3 + p + 125
+__device__ __forceinline__ void hist_f16(uint32_t u, HistLane& h) {
+  const uint32_t a = u & 0x7FFFu;
+  const uint32_t exp = a >> 10;
+  const uint32_t word =
+      exp != 0u ? exp + 137u : 159u - (uint32_t)__clz((int)a);
+  hist_elem(a, (u >> 15) & 1u, 0x7C00u, word, h);
+}
+
+// f64 pattern: binade E - 1023, or p - 1074 for a subnormal, clamped to the
+// f32 range -149..127
+__device__ __forceinline__ void hist_f64(uint32_t lo, uint32_t hi,
+                                         HistLane& h) {
+  const uint32_t ahi = hi & 0x7FFFFFFFu;
+  const unsigned long long a = ((unsigned long long)ahi << 32) | lo;
+  const int exp = (int)(ahi >> 20);
+  const int binade = exp != 0 ? exp - 1023 : 63 - __clzll((long long)a) - 1074;
+  const int k = min(max(binade + 149, 0), (int)kHistBins - 1);
+  // the classification needs "zero", "finite" and nothing else of the low
+  // word: fold it into one bit below the high word's pattern
+  const uint32_t a32 = ahi | (uint32_t)(lo != 0u);
+  // Inf is 0x7FF00000 with lo == 0, every NaN is above or has lo != 0
+  hist_elem(a32, hi >> 31, 0x7FF00000u, 3u + (uint32_t)k, h);
+}
+
+// the elements of one loaded 32-bit word (one for f32, two for f16 / bf16;
+// a bf16 pattern is the top half of the f32 pattern of the same value)
+template <uint32_t CLS>
+__device__ __forceinline__ void hist_word(uint32_t w, HistLane& h) {
+  if (CLS == kScanF32) {
+    hist_f32(w, h);
+  } else if (CLS == kScanBF16) {
+    hist_f32(w << 16, h);
+    hist_f32(w & 0xFFFF0000u, h);
+  } else {  // kScanF16
+    hist_f16(w & 0xFFFFu, h);
+    hist_f16(w >> 16, h);
+  }
+}
+
+// One naturally aligned VEC-byte load (VEC >= the element size) and every
+// element in it. A zero element counts, so the one load narrower than a word
+// (a single 16-bit element) is not padded, as in stats_vec.
+template <int VEC, uint32_t CLS>
+__device__ __forceinline__ void hist_vec(const char* p, HistLane& h) {
+  if (VEC == 16) {
+    const uint4 v = *reinterpret_cast<const uint4*>(p);
+    if (CLS == kScanF64) {
+      hist_f64(v.x, v.y, h);
+      hist_f64(v.z, v.w, h);
+    } else {
+      hist_word<CLS>(v.x, h);
+      hist_word<CLS>(v.y, h);
+      hist_word<CLS>(v.z, h);
+      hist_word<CLS>(v.w, h);
+    }
+  } else if (VEC == 8) {
+    const uint2 v = *reinterpret_cast<const uint2*>(p);
+    if (CLS == kScanF64) {
+      hist_f64(v.x, v.y, h);
+    } else {
+      hist_word<CLS>(v.x, h);
+      hist_word<CLS>(v.y, h);
+    }
+  } else if (VEC == 4) {
+    if (CLS != kScanF64) hist_word<CLS>(*reinterpret_cast<const uint32_t*>(p), h);
+  } else if (VEC == 2) {
+    const uint32_t e = *reinterpret_cast<const uint16_t*>(p);
+    if (CLS == kScanBF16) hist_f32(e << 16, h);
+    else if (CLS == kScanF16) hist_f16(e, h);
+  }
+}
+
+// The class switch sits outside the traversal, as in stats_class; the host
+// refuses vec below the element size, so those pairs are not instantiated.
+template <uint32_t CLS>
+__device__ __forceinline__ void hist_class(const Desc& d, uint32_t s,
+                                           uint32_t e, HistLane& h) {
+  constexpr uint32_t ESZ = scan_elem_size(CLS);
+  auto range = [&](auto vec) {
+    constexpr int VEC = decltype(vec)::value;
+    for_each_vec<VEC, 1, 4>(d, s, e, [&](unsigned long long, const char* p) {
+      hist_vec<VEC, CLS>(p, h);
+    });
+  };
+  switch (d.vec) {
+    case 16: range(std::integral_constant<int, 16>{}); break;
+    case 8: range(std::integral_constant<int, 8>{}); break;
+    case 4:
+      if constexpr (ESZ <= 4) range(std::integral_constant<int, 4>{});
+      break;
+    default:
+      if constexpr (ESZ <= 2) range(std::integral_constant<int, 2>{});
+      break;
+  }
+}
+
+// Reduce the copies into out[0 .. kHistWords) and leave them cleared. Every
+// thread of the workgroup must call it (two barriers). Thread t owns words
+// t, t + 256, ...: it reads and clears the 32 copies of a word starting at
+// copy (t & 31), so that the lanes of a half wave, which hold 32 consecutive
+// words, read 32 different banks in every step and not one.
+__device__ __forceinline__ void hist_flush(uint32_t* bins, HistLane& h,
+                                           unsigned long long* out) {
+  if (h.n_negative != 0u) atomicAdd(&h.mine[1u * kHistCopies], h.n_negative);
+  h.n_negative = 0u;
+  __syncthreads();  // every lane's increments are in
+  for (uint32_t w = threadIdx.x; w < kHistWords; w += kBlockThreads) {
+    unsigned long long total = 0;
+#pragma unroll 8
+    for (uint32_t i = 0; i < kHistCopies; ++i) {
+      uint32_t* p = &bins[w * kHistCopies + ((w + i) & (kHistCopies - 1u))];
+      total += *p;
+      *p = 0u;
+    }
+    if (total != 0ull) atomicAdd(&out[w], total);
+  }
+  __syncthreads();  // cleared before anybody counts again
+}
+
+// out[280 * i ..]: the words of descriptor i, zeroed by the launcher.
+__global__ __launch_bounds__(kBlockThreads) void hist_kernel(
+    const Desc* __restrict__ descs, const uint32_t* __restrict__ classes,
+    int n, const unsigned long long* __restrict__ wu_prefix,
+    unsigned long long total_wus, unsigned long long* __restrict__ out) {
+  __shared__ uint32_t bins[kHistWords * kHistCopies];
+  for (uint32_t i = threadIdx.x; i < kHistWords * kHistCopies;
+       i += kBlockThreads) {
+    bins[i] = 0u;
+  }
+  __syncthreads();
+  HistLane h{&bins[threadIdx.x & (kHistCopies - 1u)], 0u};
+  int cur = -1;
+  for_each_work_unit(
+      descs, n, wu_prefix, total_wus,
+      [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
+        if (owner != cur) {
+          // uniform: owner and cur are the same in every thread
+          if (cur >= 0) hist_flush(bins, h, &out[(size_t)kHistWords * cur]);
+          cur = owner;
+        }
+        switch (classes[owner]) {
+          case kScanF64: hist_class<kScanF64>(d, s, e, h); break;
+          case kScanF32: hist_class<kScanF32>(d, s, e, h); break;
+          case kScanF16: hist_class<kScanF16>(d, s, e, h); break;
+          default: hist_class<kScanBF16>(d, s, e, h); break;
+        }
+      });
+  if (cur >= 0) hist_flush(bins, h, &out[(size_t)kHistWords * cur]);
+}
+
+// ---------------------------------------------------------------------------
 // compare: a stored payload against live tensors, element by element, with
 // BOTH sides read-only. The flat side is the payload where the storage read
 // put it (the consumer's pinned host block, read once over PCIe, or a device
@@ -2199,6 +2448,59 @@ static std::vector<unsigned long long> tensor_stats(
 }
 
 // ---------------------------------------------------------------------------
+// exponent histograms of N strided device tensors (blocking): one launch of
+// hist_kernel. `flat` and `classes` are tensor_stats' and are validated
+// under its rules (DescKind::Stats: no rule differs, so a refusal reads
+// "tensor_stats: ..."). Returns 280*n words (see hist_kernel), all zero for a
+// descriptor without elements. `max_grid` > 0 bounds the workgroups below
+// the cap; no word depends on it.
+// ---------------------------------------------------------------------------
+
+static std::vector<unsigned long long> tensor_hist(
+    const std::vector<unsigned long long>& flat, int n,
+    const std::vector<uint32_t>& classes, int device,
+    uintptr_t producer_stream, unsigned int max_grid) {
+  const std::vector<Desc> descs = parse_descs(flat, n);
+  check_descs(descs, DescKind::Stats, nullptr, &classes);
+
+  const size_t n_results = (size_t)kHistWords * (size_t)n;
+  const std::vector<unsigned long long> wu_prefix = wu_prefix_of(descs);
+  const unsigned long long total_wus = wu_prefix[n];
+  if (total_wus == 0) return std::vector<unsigned long long>(n_results, 0);
+
+  // descriptors | prefix sums | classes
+  const LaunchTables tables(descs, wu_prefix, classes.data(),
+                            sizeof(uint32_t) * n);
+
+  // 35 KiB of LDS per workgroup lets four be resident on each of the 256
+  // CUs: 1024 workgroups fill the device exactly once. More would only
+  // queue behind them, and each workgroup pays for its counters per
+  // descriptor it visits: a clear and a reduction of 8960 LDS words and up
+  // to 280 global atomics. With the cap at one resident round a workgroup
+  // stays on a large tensor for as many work units as possible and the
+  // global atomics per tensor are bounded by 1024 * (occupied bins).
+  // TSAMD_PACK_GRID replaces the cap only when the caller names no bound.
+  constexpr unsigned long long kHistGridCap = 1024;
+  const unsigned int grid =
+      max_grid > 0
+          ? grid_for(total_wus,
+                     max_grid < kHistGridCap ? max_grid : kHistGridCap,
+                     nullptr)
+          : grid_for(total_wus, kHistGridCap, getenv("TSAMD_PACK_GRID"));
+
+  return read_launch(
+      tables, n_results, producer_stream, device, "tensor_hist: ",
+      [&](const void* d_tables, unsigned long long* d_out,
+          hipStream_t stream) {
+        hipLaunchKernelGGL(
+            hist_kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
+            tables.descs(d_tables),
+            static_cast<const uint32_t*>(tables.extra(d_tables)), n,
+            tables.prefix(d_tables), total_wus, d_out);
+      });
+}
+
+// ---------------------------------------------------------------------------
 // a stored payload against N live strided device tensors (blocking): one
 // launch of compare_kernel and one of compare_finish_kernel for all the
 // members of one read. `flat` holds unpack-style descriptor rows (flat_off
@@ -2518,6 +2820,13 @@ PYBIND11_MODULE(_csnap, m) {
         "elements, read in place (blocking); six words per descriptor: "
         "n_finite, n_zero, min key, max key, sum and sum of squares as f64 "
         "bits; max_grid > 0 bounds the workgroups",
+        py::arg("flat"), py::arg("n"), py::arg("classes"), py::arg("device"),
+        py::arg("stream"), py::arg("max_grid") = 0);
+  m.def("tensor_hist", &tensor_hist,
+        "exponent histograms of strided device tensors, read in place "
+        "(blocking); 280 words per descriptor: n_zero, n_negative, "
+        "n_nonfinite, then the count of finite non-zero elements per binade "
+        "floor(log2|x|) = -149..127; max_grid > 0 bounds the workgroups",
         py::arg("flat"), py::arg("n"), py::arg("classes"), py::arg("device"),
         py::arg("stream"), py::arg("max_grid") = 0);
   m.def("compare_tensors", &compare_tensors,

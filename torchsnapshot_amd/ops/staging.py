@@ -824,6 +824,71 @@ def host_tensor_stats(
 
 
 # ---------------------------------------------------------------------------
+# exponent histograms: the 280 words, host fallbacks
+# ---------------------------------------------------------------------------
+
+# HIST_WORDS u64 words per tensor (hist_kernel in ops/hip/staging.hip):
+# n_zero (+0 and -0), n_negative (finite, non-zero, sign set), n_nonfinite,
+# then for k = 0..276 the finite non-zero elements with
+# floor(log2|x|) == k + HIST_MIN_EXP. The bins are float32's binades,
+# subnormal ones included; a float64 element outside counts in the end bin.
+# words[0] + words[2] + sum(words[3:]) is the element count. Descriptors and
+# classes are the statistics' (build_stats_items); all words are counts, so
+# the words of disjoint sets of elements add.
+HIST_WORDS = 280
+HIST_MIN_EXP = -149
+HIST_MAX_EXP = 127
+
+
+def decode_hist(words: Sequence[int]) -> Dict[str, Any]:
+    """``{n, n_zero, n_negative, n_nonfinite, bins}`` of the 280 words;
+    ``bins`` is ``{floor(log2|x|): count}`` for the non-empty bins."""
+    bins = {k + HIST_MIN_EXP: int(c) for k, c in enumerate(words[3:]) if c}
+    return {
+        "n": int(words[0]) + int(words[2]) + sum(bins.values()),
+        "n_zero": int(words[0]),
+        "n_negative": int(words[1]),
+        "n_nonfinite": int(words[2]),
+        "bins": bins,
+    }
+
+
+def torch_tensor_hist(
+    t: torch.Tensor, stored_dtype: Optional[torch.dtype] = None
+) -> List[int]:
+    """The 280 words by torch expressions, on the tensor's own device: what
+    the histogram kernel must agree with exactly, and the path for anything
+    it declines. The binade comes from ``torch.frexp`` of the values in
+    float64, which holds all four dtypes exactly and in which a float32 or
+    16-bit subnormal is a normal number. All zeros for a tensor that gets no
+    histogram. ``stored_dtype`` is ignored: the values are the live ones."""
+    view = _stats_view(t)
+    if view is None:
+        return [0] * HIST_WORDS
+    x = resolve_lazy(view).to(torch.float64).reshape(-1)
+    finite = torch.isfinite(x)
+    counted = x[finite & (x != 0)]
+    # |x| = m * 2^e with m in [0.5, 1): floor(log2|x|) is e - 1
+    k = (torch.frexp(counted).exponent.to(torch.int64) - 1 - HIST_MIN_EXP).clamp_(
+        0, HIST_MAX_EXP - HIST_MIN_EXP
+    )
+    bins = torch.bincount(k, minlength=HIST_WORDS - 3)
+    return [
+        int((x == 0).sum()),
+        int((counted < 0).sum()),
+        int((~finite).sum()),
+        *bins.tolist(),
+    ]
+
+
+def host_tensor_hist(
+    t: torch.Tensor, stored_dtype: Optional[torch.dtype] = None
+) -> List[int]:
+    """torch_tensor_hist() on the host: the path for host tensors."""
+    return torch_tensor_hist(t.detach().cpu(), stored_dtype)
+
+
+# ---------------------------------------------------------------------------
 # compare: descriptors, the six fields, the torch expression
 # ---------------------------------------------------------------------------
 
@@ -1545,6 +1610,48 @@ class StagingEngine:
             lambda i: torch_tensor_stats(tensors[i]),
             merge=merge_stats,
             empty=STATS_EMPTY,
+        )
+        return [list(row) for row in zip(*columns)] if tensors else []
+
+    # -- exponent histograms --------------------------------------------------
+
+    def hist(
+        self,
+        tensors: Sequence[torch.Tensor],
+        stored_dtypes: Optional[Sequence[Optional[torch.dtype]]] = None,
+        max_grid: int = 0,
+    ) -> List[List[int]]:
+        """The 280 histogram words (decode_hist) of each of this device's
+        ``tensors``, from ONE read-only launch of the histogram kernel over
+        all of them. Blocking.
+
+        Every word is an exact count: the same tensor gives the same words
+        whatever else is in the batch and whatever ``max_grid`` (a bound on
+        the kernel's workgroups, 0 = the extension's cap) says. The words of
+        a tensor over the kernel's size cap are the sums of its dim-0
+        pieces'. The values are the live ones: ``stored_dtypes`` is accepted
+        for state_checks.UniqueTensors.read and ignored. fp8, complex,
+        integer, quantized and sparse tensors report zeros.
+
+        Tensors build_stats_items() declines are computed with torch
+        expressions instead; so is everything when the extension is
+        disabled by TSAMD_DISABLE_HIP_STAGING=1."""
+        if not self._use_ext:
+            return [torch_tensor_hist(t) for t in tensors]
+        per_tensor, classes = build_stats_items(tensors)
+        columns = self._read_launch(
+            # without a class there is nothing to report, and no fallback
+            [[] if cls is None else its for its, cls in zip(per_tensor, classes)],
+            lambda items, owners, stream, dev_index: _csnap.tensor_hist(
+                _items_to_flat(items),
+                len(items),
+                [classes[i] for i in owners],
+                dev_index,
+                stream,
+                max_grid,
+            ),
+            HIST_WORDS,
+            lambda i: torch_tensor_hist(tensors[i]),
         )
         return [list(row) for row in zip(*columns)] if tensors else []
 

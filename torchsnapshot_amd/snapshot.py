@@ -39,6 +39,7 @@ from . import (
     knobs,
     nonfinite as _nonfinite,
     replication as _replication,
+    tensor_hist as _tensor_hist,
     tensor_stats as _tensor_stats,
 )
 from .dist_store import LinearBarrier, get_or_create_store
@@ -226,16 +227,27 @@ class Snapshot:
     def get_stats(self) -> Dict[str, "_tensor_stats.TensorStats"]:
         """``{logical_path: TensorStats}`` as recorded by
         ``take(..., stats=True)``; empty for a snapshot taken without."""
+        buf = self._read_sidecar(_tensor_stats.SIDECAR_FILENAME)
+        return {} if buf is None else _tensor_stats.decode_sidecar(buf)
+
+    def get_histograms(self) -> Dict[str, "_tensor_hist.TensorHistogram"]:
+        """``{logical_path: TensorHistogram}`` as recorded by
+        ``take(..., histogram=True)``; empty for a snapshot taken without."""
+        buf = self._read_sidecar(_tensor_hist.SIDECAR_FILENAME)
+        return {} if buf is None else _tensor_hist.decode_sidecar(buf)
+
+    def _read_sidecar(self, name: str) -> Optional[bytes]:
+        """The bytes of a sidecar beside the manifest, None without one."""
         from .io_types import ReadIO
 
         storage = url_to_storage_plugin(self.path, self._storage_options)
         try:
-            read_io = ReadIO(path=_tensor_stats.SIDECAR_FILENAME)
+            read_io = ReadIO(path=name)
             try:
                 storage.sync_read(read_io)
             except FileNotFoundError:
-                return {}
-            return _tensor_stats.decode_sidecar(bytes(read_io.buf))
+                return None
+            return bytes(read_io.buf)
         finally:
             storage.sync_close()
 
@@ -274,6 +286,7 @@ class Snapshot:
         replicated_check: Optional[str] = None,
         *,
         stats: bool = False,
+        histogram: bool = False,
     ) -> "Snapshot":
         """``save_dtype``: store float32 tensors narrowed to
         ``torch.bfloat16`` / ``torch.float16`` — one dtype for everything,
@@ -305,7 +318,14 @@ class Snapshot:
         (:meth:`get_stats`). They are statistics of the live values, not of
         a ``save_dtype`` narrowing; device tensors are read in place by one
         kernel launch per device. Off by default: nothing runs and no
-        sidecar is written."""
+        sidecar is written.
+
+        ``histogram``: record, for the same leaves, how many elements lie in
+        each binade ``floor(log2|x|)`` and how many are zero, negative or
+        non-finite, in a ``.tensor_hist`` sidecar (:meth:`get_histograms`;
+        ``TensorHistogram.narrowing(dtype)`` says what a narrowing would
+        lose). Live values, one more kernel launch per device, off by
+        default like ``stats``."""
         torch._C._log_api_usage_once("torchsnapshot_amd.Snapshot.take")
         cls._validate_app_state(app_state)
         save_dtype_rules = _normalize_save_dtype(save_dtype)
@@ -333,6 +353,7 @@ class Snapshot:
                     nonfinite_policy=nonfinite_policy,
                     replicated_policy=replicated_policy,
                     stats=stats,
+                    histogram=histogram,
                 )
                 pending_io_work.complete()
                 from .integrity import write_checksum_file
@@ -365,9 +386,10 @@ class Snapshot:
         replicated_check: Optional[str] = None,
         *,
         stats: bool = False,
+        histogram: bool = False,
     ) -> "PendingSnapshot":
         """See :meth:`take` for ``save_dtype``, ``nonfinite``,
-        ``replicated_check`` and ``stats``; a :class:`NonFiniteStateError` or
+        ``replicated_check``, ``stats`` and ``histogram``; a :class:`NonFiniteStateError` or
         :class:`ReplicatedStateMismatchError` is raised here, not by the
         pending snapshot."""
         torch._C._log_api_usage_once("torchsnapshot_amd.Snapshot.async_take")
@@ -411,6 +433,7 @@ class Snapshot:
                 nonfinite_policy=nonfinite_policy,
                 replicated_policy=replicated_policy,
                 stats=stats,
+                histogram=histogram,
             )
             # once staging is complete, the app may mutate its state
             # freely. With shadow clones (sources_immutable) there is
@@ -453,6 +476,7 @@ class Snapshot:
         nonfinite_policy: str = "ignore",
         replicated_policy: str = "ignore",
         stats: bool = False,
+        histogram: bool = False,
     ) -> Tuple[PendingIOWork, SnapshotMetadata]:
         rank = pg_wrapper.get_rank()
         world_size = pg_wrapper.get_world_size()
@@ -536,6 +560,10 @@ class Snapshot:
         # reports are exchanged here, on the calling thread, and rank 0
         # writes the merged result below once the old commit is gone.
         collected = _tensor_stats.collect(flattened, pg_wrapper) if stats else None
+        # and the fourth, under the same rules: the exponent histograms
+        histograms = (
+            _tensor_hist.collect(flattened, pg_wrapper) if histogram else None
+        )
 
         write_reqs: List[WriteReq] = []
         req_to_logical: Dict[str, str] = {}
@@ -602,7 +630,11 @@ class Snapshot:
         # plausible length. The manifest all-gather below orders this
         # before any rank's first payload write.
         if rank == 0:
-            cls._uncommit(storage, keep_stats=collected is not None)
+            cls._uncommit(
+                storage,
+                keep_stats=collected is not None,
+                keep_hist=histograms is not None,
+            )
             if collected is not None:
                 # before .snapshot_metadata: a committed snapshot that asked
                 # for statistics has them
@@ -610,6 +642,13 @@ class Snapshot:
                     WriteIO(
                         path=_tensor_stats.SIDECAR_FILENAME,
                         buf=_tensor_stats.encode_sidecar(collected),
+                    )
+                )
+            if histograms is not None:
+                storage.sync_write(
+                    WriteIO(
+                        path=_tensor_hist.SIDECAR_FILENAME,
+                        buf=_tensor_hist.encode_sidecar(histograms),
                     )
                 )
 
@@ -628,21 +667,29 @@ class Snapshot:
         return pending, metadata
 
     @staticmethod
-    def _uncommit(storage: StoragePlugin, keep_stats: bool = False) -> None:
+    def _uncommit(
+        storage: StoragePlugin, keep_stats: bool = False, keep_hist: bool = False
+    ) -> None:
         """Remove an existing ``.snapshot_metadata`` under a filesystem
         snapshot path (a missing one is fine). Object stores replace whole
         objects and never expose a half-written one, so only the FS plugin
-        needs this. The ``.tensor_stats`` sidecar of the old commit goes
-        with it, on any storage, unless this save is about to replace it
-        (``keep_stats``): statistics never outlive the state they are of."""
+        needs this. The ``.tensor_stats`` and ``.tensor_hist`` sidecars of
+        the old commit go with it, on any storage, unless this save is about
+        to replace them (``keep_stats``, ``keep_hist``): neither outlives the
+        state it is of. A missing one is fine."""
         from .storage.fs import FSStoragePlugin
 
         if not isinstance(storage, FSStoragePlugin):
-            if not keep_stats:
-                from .scheduler import run_coro_sync
+            from .scheduler import run_coro_sync
 
+            for name, keep in (
+                (_tensor_stats.SIDECAR_FILENAME, keep_stats),
+                (_tensor_hist.SIDECAR_FILENAME, keep_hist),
+            ):
+                if keep:
+                    continue
                 try:
-                    run_coro_sync(storage.delete(_tensor_stats.SIDECAR_FILENAME))
+                    run_coro_sync(storage.delete(name))
                 except FileNotFoundError:
                     # every plugin here reports a missing object this way
                     # (the object stores' delete accepts a 404 itself); any
@@ -650,7 +697,11 @@ class Snapshot:
                     # new state, so it fails the save
                     pass
             return
-        for name in (_tensor_stats.SIDECAR_FILENAME, METADATA_FILENAME):
+        for name in (
+            _tensor_stats.SIDECAR_FILENAME,
+            _tensor_hist.SIDECAR_FILENAME,
+            METADATA_FILENAME,
+        ):
             try:
                 os.remove(os.path.join(storage.root, name))
             except FileNotFoundError:
