@@ -7,12 +7,21 @@
               a half-size device copy of the state, then the usual staging
   save_dtype  save_dtype=torch.bfloat16 — the cast runs inside the staging
               gather kernel on the side stream
+  mx          save_dtype="mxfp8_e4m3" — block-scaled fp8, quantised inside
+              the gather kernel; 33 bytes stored per 32 elements. With
+              --dtype bfloat16 the state is bf16 and only fp32 (here: the
+              plain save) and mx run
 
 Part "save" reports the wall time of Snapshot.take and the stall of
 Snapshot.async_take for each (median of --reps after --warmup, variants
 interleaved so disk state drifts hit all three alike). Part "stage" reports
 the stage-only rate of engine.stage + wait on a 1 GiB fp32 tensor, cast vs
 uncast, direct vs slab mode, in SOURCE bytes per second.
+
+Part "mx_stage" (run with --part mx_stage, not part of "all") reports
+engine.stage + wait of --members tensors of 4096 x 4096 in one launch,
+bf16 and fp32, plain against mxfp8_e4m3: time, stored bytes and the D2H
+rate in stored bytes (profiles/mx_save_measurements.md).
 
 Each part runs in a fresh child process: the stage part sizes the pinned
 pool's blocks to hold 1 GiB so no run pays a one-off pinned allocation.
@@ -53,11 +62,12 @@ def part_save(args) -> dict:
     from torchsnapshot_amd.state_dict import StateDict
 
     device = torch.device("cuda", 0)
-    per = 64 * MIB // 4  # 64 MiB fp32 per tensor
+    dtype = getattr(torch, args.dtype)
+    per = 64 * MIB // dtype.itemsize  # 64 MiB per tensor
     n_tensors = max(int(args.state_gib * GIB) // (64 * MIB), 1)
     sd = StateDict(
         **{
-            f"w{i}": torch.randn(per, dtype=torch.float32, device=device)
+            f"w{i}": torch.randn(per, dtype=torch.float32, device=device).to(dtype)
             for i in range(n_tensors)
         }
     )
@@ -68,7 +78,10 @@ def part_save(args) -> dict:
             "_custom_tensor_prepare_func": lambda p, t: t.to(torch.bfloat16)
         },
         "save_dtype": {"save_dtype": torch.bfloat16},
+        "mx": {"save_dtype": "mxfp8_e4m3"},
     }
+    if dtype != torch.float32:
+        variants = {k: variants[k] for k in ("fp32", "mx")}
     take_s = {k: [] for k in variants}
     stall_s = {k: [] for k in variants}
     async_total_s = {k: [] for k in variants}
@@ -125,6 +138,7 @@ def part_stage(args) -> dict:
         "uncast_kernel": (halves, None),
         "cast_kernel": (halves, [torch.bfloat16, torch.bfloat16]),
         "cast_kernel_single": ([t], [torch.bfloat16]),
+        "mx_kernel": (halves, ["mxfp8_e4m3", "mxfp8_e4m3"]),
     }
     out = {"part": "stage", "source_bytes": GIB, "cases": {}}
     for mode in ("direct", "slab"):
@@ -149,13 +163,58 @@ def part_stage(args) -> dict:
     return out
 
 
+def part_mx_stage(args) -> dict:
+    import torch
+
+    from torchsnapshot_amd.ops import staging
+
+    device = torch.device("cuda", 0)
+    engine = staging.get_staging_engine(device)
+    staging.warm_pinned_pool(4 * GIB, background=False)
+    out = {"part": "mx_stage", "members": args.members, "cases": {}}
+    for dtype in (torch.bfloat16, torch.float32):
+        tensors = [
+            torch.randn(4096, 4096, device=device).to(dtype)
+            for _ in range(args.members)
+        ]
+        src = sum(t.numel() * t.element_size() for t in tensors)
+        for name, outs in (("plain", None), ("mx", ["mxfp8_e4m3"] * len(tensors))):
+            times = []
+            for rep in range(args.warmup + args.reps):
+                torch.cuda.synchronize()
+                t0 = time.monotonic()
+                batch = engine.stage(tensors, out_dtypes=outs)
+                batch.wait()
+                dt = time.monotonic() - t0
+                stored = batch.total_bytes
+                batch.release()
+                if rep >= args.warmup:
+                    times.append(dt)
+            r = _summary(times)
+            r.update(source_bytes=src, stored_bytes=stored)
+            key = f"{str(dtype).removeprefix('torch.')}/{name}"
+            out["cases"][key] = r
+            print(
+                f"{key:>16}: {r['median'] * 1e3:.2f} ms [{r['min'] * 1e3:.2f}.."
+                f"{r['max'] * 1e3:.2f}]  stored {stored / MIB:.0f} MiB  "
+                f"{stored / r['median'] / 1e9:.1f} GB/s stored, "
+                f"{src / r['median'] / 1e9:.1f} GB/s of source"
+            )
+        del tensors
+    return out
+
+
 def main() -> None:
     parser = argparse.ArgumentParser()
     parser.add_argument("--work-dir", default="/tmp/tsamd_cast_save_bench")
     parser.add_argument("--state-gib", type=float, default=4.0)
     parser.add_argument("--reps", type=int, default=5)
     parser.add_argument("--warmup", type=int, default=2)
-    parser.add_argument("--part", choices=["all", "save", "stage"], default="all")
+    parser.add_argument("--dtype", choices=["float32", "bfloat16"], default="float32")
+    parser.add_argument("--members", type=int, default=8)
+    parser.add_argument(
+        "--part", choices=["all", "save", "stage", "mx_stage"], default="all"
+    )
     args = parser.parse_args()
 
     if args.part == "all":
@@ -167,6 +226,7 @@ def main() -> None:
                 "--state-gib", str(args.state_gib),
                 "--reps", str(args.reps),
                 "--warmup", str(args.warmup),
+                "--dtype", args.dtype,
                 "--part", part,
             ]
             subprocess.run(cmd, check=True)
@@ -176,6 +236,8 @@ def main() -> None:
             "TSAMD_PINNED_BLOCK_SIZE_BYTES", str(GIB + 4096)
         )
         result = part_stage(args)
+    elif args.part == "mx_stage":
+        result = part_mx_stage(args)
     else:
         result = part_save(args)
     print(json.dumps(result))

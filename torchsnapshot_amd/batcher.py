@@ -41,6 +41,8 @@ from .ops.staging import (
     HIP_EXT_AVAILABLE,
     build_pack_items,
     get_staging_engine,
+    is_mx,
+    mx_encode,
     resolve_lazy,
 )
 from .serialization import SERIALIZER_BUFFER, tensor_as_memoryview
@@ -180,7 +182,9 @@ class BatchedBufferStager(BufferStager):
         members = []
         for t, off, out_dtype in zip(self.tensors, offsets, self.out_dtypes):
             t = resolve_lazy(t)  # lazy conj/neg views are saved by value
-            if out_dtype is not None and out_dtype != t.dtype:
+            if is_mx(out_dtype):
+                t = mx_encode(t)  # the payload, as uint8
+            elif out_dtype is not None and out_dtype != t.dtype:
                 t = t.to(out_dtype)
             nbytes = t.numel() * t.element_size()
             if nbytes == 0:

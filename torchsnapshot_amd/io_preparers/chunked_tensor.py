@@ -15,7 +15,8 @@ import torch
 from .. import knobs
 from ..io_types import ReadReq, WriteReq
 from ..manifest import ChunkedTensorEntry, Shard
-from ..serialization import dtype_to_str, str_to_dtype
+from ..ops.staging import is_mx
+from ..serialization import dtype_to_str, entry_tensor_dtype
 from .tensor import LoadFuture, TensorIOPreparer, tensor_copy
 
 
@@ -83,6 +84,7 @@ class ChunkedTensorIOPreparer:
             shape=list(tensor.shape),
             chunks=chunks,
             replicated=replicated,
+            logical_dtype=dtype_to_str(tensor.dtype) if is_mx(save_dtype) else None,
         )
         return entry, write_reqs
 
@@ -95,9 +97,7 @@ class ChunkedTensorIOPreparer:
         if tensor_out is None or list(tensor_out.shape) != list(entry.shape):
             # shape mismatch (elasticity) or no target: stage into a fresh
             # tensor, then copy what overlaps at the end if a target exists
-            staging = torch.empty(
-                entry.shape, dtype=str_to_dtype(entry.dtype)
-            )
+            staging = torch.empty(entry.shape, dtype=entry_tensor_dtype(entry))
             dst = staging
             final_out = tensor_out
         else:

@@ -30,8 +30,12 @@ from ..manifest import TensorEntry
 from ..ops.staging import (
     HIP_EXT_AVAILABLE,
     get_staging_engine,
+    is_mx,
+    mx_decode,
+    mx_encode,
     resolve_lazy,
     scatter_member,
+    stored_nbytes,
     torch_tensor_diff,
 )
 from ..serialization import (
@@ -39,6 +43,7 @@ from ..serialization import (
     SERIALIZER_QTENSOR,
     SERIALIZER_TORCH_SAVE,
     dtype_to_str,
+    entry_tensor_dtype,
     pick_serializer,
     qtensor_as_bytes,
     qtensor_from_bytes,
@@ -99,7 +104,8 @@ class TensorIOPreparer:
     ) -> Tuple[TensorEntry, List[WriteReq]]:
         """``save_dtype`` stores the tensor narrowed to that dtype (the
         entry records the STORED dtype); it requires the plain buffer
-        serializer."""
+        serializer. Under ``"mxfp8_e4m3"`` the entry also records the
+        tensor's own dtype as ``logical_dtype``."""
         serializer = pick_serializer(tensor)
         if save_dtype == tensor.dtype:
             save_dtype = None
@@ -114,6 +120,7 @@ class TensorIOPreparer:
             dtype=dtype_to_str(save_dtype or tensor.dtype),
             shape=list(tensor.shape),
             replicated=replicated,
+            logical_dtype=dtype_to_str(tensor.dtype) if is_mx(save_dtype) else None,
         )
         stager = TensorBufferStager(
             tensor=tensor,
@@ -137,6 +144,9 @@ class TensorIOPreparer:
             and entry.serializer == SERIALIZER_BUFFER
             and entry.byte_range is None
             and nbytes > buffer_size_limit_bytes
+            # a block-scaled payload is read whole: its scales sit behind
+            # its codes
+            and not is_mx(entry.dtype)
         ):
             return TensorIOPreparer._prepare_read_tiled(
                 entry, tensor_out, buffer_size_limit_bytes
@@ -286,12 +296,10 @@ class TensorBufferStager(BufferStager):
 
     def stored_nbytes(self) -> int:
         """Payload bytes as written (after the save_dtype cast, if any)."""
-        esz = (
-            self.save_dtype.itemsize
-            if self.save_dtype is not None
-            else self.tensor.element_size()
+        return stored_nbytes(
+            self.tensor.numel(),
+            self.save_dtype if self.save_dtype is not None else self.tensor.dtype,
         )
-        return self.tensor.numel() * esz
 
     def get_staging_cost_bytes(self) -> int:
         nbytes = self.stored_nbytes()
@@ -323,9 +331,7 @@ class TensorBufferStager(BufferStager):
             cpu = uvm_to_cpu(t)
             if self.save_dtype is not None:
                 # the cast result is already a private copy
-                return tensor_as_memoryview(
-                    cpu.to(self.save_dtype).contiguous()
-                )
+                return tensor_as_memoryview(self._cast_on_host(cpu))
             if self.is_async_snapshot:
                 cpu = cpu.clone()
             return tensor_as_memoryview(cpu.contiguous())
@@ -354,13 +360,19 @@ class TensorBufferStager(BufferStager):
         if self.save_dtype is not None:
             # runs on the executor thread; the cast result is a private
             # copy, so async snapshots need no extra clone
-            return tensor_as_memoryview(t.to(self.save_dtype).contiguous())
+            return tensor_as_memoryview(self._cast_on_host(t))
         # a resolved lazy view is a private copy already
         if t is src and self._should_copy_cpu_tensor(t, ctx):
             t = t.contiguous().clone() if not t.is_contiguous() else t.clone()
         elif not t.is_contiguous():
             t = t.contiguous()
         return tensor_as_memoryview(t)
+
+    def _cast_on_host(self, t: torch.Tensor) -> torch.Tensor:
+        """``t`` as it is stored under save_dtype, by torch."""
+        if is_mx(self.save_dtype):
+            return mx_encode(t)
+        return t.to(self.save_dtype).contiguous()
 
     def _should_copy_cpu_tensor(self, t: torch.Tensor, ctx: StageContext) -> bool:
         # Async snapshots: training resumes (and may mutate the tensor) as
@@ -401,6 +413,22 @@ class TensorBufferConsumer(PinnedReadConsumer):
             return 2 * nbytes
         return nbytes
 
+    def _stored_dtype(self):
+        """The payload's dtype as the engine names it: a torch.dtype, or the
+        string of the block-scaled format."""
+        if is_mx(self.entry.dtype):
+            return self.entry.dtype
+        return str_to_dtype(self.entry.dtype)
+
+    def _decode_mx(self, u8: torch.Tensor) -> torch.Tensor:
+        """A block-scaled payload as a ``logical_dtype`` tensor of the
+        entry's shape, by torch, on the payload's device."""
+        n = 1
+        for s in self.entry.shape:
+            n *= s
+        flat = mx_decode(u8, n, entry_tensor_dtype(self.entry))
+        return flat.reshape(tuple(self.entry.shape))
+
     def device_span_target(self):
         if (
             self.tensor_out is not None
@@ -439,15 +467,16 @@ class TensorBufferConsumer(PinnedReadConsumer):
             or list(out.shape) != list(self.entry.shape)
         ):
             return None
-        member = scatter_member(
-            out.detach(), str_to_dtype(self.entry.dtype), base_offset
-        )
+        member = scatter_member(out.detach(), self._stored_dtype(), base_offset)
         return None if member is None else [member]
 
     def consume_from_device_u8(self, dev_u8: torch.Tensor) -> None:
-        loaded = view_payload(
-            dev_u8, str_to_dtype(self.entry.dtype), self.entry.shape
-        )
+        if is_mx(self.entry.dtype):
+            loaded = self._decode_mx(dev_u8)
+        else:
+            loaded = view_payload(
+                dev_u8, str_to_dtype(self.entry.dtype), self.entry.shape
+            )
         tensor_copy(self.tensor_out, loaded)
         self.fut.obj = self.tensor_out
 
@@ -478,6 +507,10 @@ class TensorBufferConsumer(PinnedReadConsumer):
                     self.fut.obj = out
                     return
                 return self.consume_from_device_u8(dev_u8)
+            elif is_mx(self.entry.dtype):
+                loaded = self._decode_mx(
+                    torch.frombuffer(memoryview(buf), dtype=torch.uint8)
+                )
             else:
                 loaded = tensor_from_memoryview(
                     memoryview(buf),

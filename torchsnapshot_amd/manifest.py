@@ -49,15 +49,20 @@ class TensorEntry:
     shape: List[int]
     replicated: bool = False
     byte_range: Optional[List[int]] = None
+    # set with dtype "mxfp8_e4m3" (docs/format.md): the dtype of the tensor
+    # that was saved, and of what a read without a target returns
+    logical_dtype: Optional[str] = None
 
     KIND = "tensor"
 
     def nbytes_estimate(self) -> int:
-        from .serialization import dtype_size_bytes
+        from .serialization import MXFP8_E4M3, dtype_size_bytes
 
         n = 1
         for s in self.shape:
             n *= s
+        if self.dtype == MXFP8_E4M3:
+            return 33 * ((n + 31) // 32)
         return n * dtype_size_bytes(self.dtype)
 
     def to_dict(self) -> Dict[str, Any]:
@@ -71,6 +76,8 @@ class TensorEntry:
         }
         if self.byte_range is not None:
             d["byte_range"] = self.byte_range
+        if self.logical_dtype is not None:
+            d["logical_dtype"] = self.logical_dtype
         return d
 
     @classmethod
@@ -82,6 +89,7 @@ class TensorEntry:
             shape=list(d["shape"]),
             replicated=bool(d.get("replicated", False)),
             byte_range=list(d["byte_range"]) if d.get("byte_range") else None,
+            logical_dtype=d.get("logical_dtype"),
         )
 
 
@@ -118,17 +126,21 @@ class ChunkedTensorEntry:
     shape: List[int]
     chunks: List[Shard]
     replicated: bool = False
+    logical_dtype: Optional[str] = None  # as in TensorEntry
 
     KIND = "chunked_tensor"
 
     def to_dict(self) -> Dict[str, Any]:
-        return {
+        d = {
             "kind": self.KIND,
             "dtype": self.dtype,
             "shape": self.shape,
             "chunks": [c.to_dict() for c in self.chunks],
             "replicated": self.replicated,
         }
+        if self.logical_dtype is not None:
+            d["logical_dtype"] = self.logical_dtype
+        return d
 
     @classmethod
     def from_dict(cls, d: Dict[str, Any]) -> "ChunkedTensorEntry":
@@ -137,6 +149,7 @@ class ChunkedTensorEntry:
             shape=list(d["shape"]),
             chunks=[Shard.from_dict(c) for c in d["chunks"]],
             replicated=bool(d.get("replicated", False)),
+            logical_dtype=d.get("logical_dtype"),
         )
 
 

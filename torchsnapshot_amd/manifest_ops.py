@@ -116,6 +116,7 @@ def _merge_replicated_entries(entries: List[Entry]) -> Entry:
             shape=first.shape,
             chunks=chunks,
             replicated=True,
+            logical_dtype=first.logical_dtype,
         )
     return first
 

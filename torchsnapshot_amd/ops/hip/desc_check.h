@@ -52,6 +52,13 @@ struct Desc {
   // Scatter only: 3 bf16->f32, 4 f16->f32 widening, same convention (flat
   // side in stored 2-byte units, tensor side in f32 bytes): a lane reads
   // `vec` stored bytes and writes 2*vec.
+  // Block-scaled fp8 (mxfp8_e4m3, codes 16..19): the flat side is one byte per
+  // element. nbytes = 32 * ceil(n / 32) is the CODES region, padded to whole
+  // blocks; the block scales, nbytes / 32 bytes, follow it at flat_off +
+  // nbytes. row_bytes is the innermost run in ELEMENTS and n = row_bytes x
+  // the outer sizes; tensor_base and strides stay in source (f32 or bf16)
+  // bytes. vec names the class: 8 = aligned (four lanes per block, 8
+  // elements each), 1 = general (one lane per block).
   uint32_t cast;
 };
 
@@ -60,6 +67,19 @@ constexpr uint32_t kCastBF16 = 1;
 constexpr uint32_t kCastF16 = 2;
 constexpr uint32_t kCastBF16toF32 = 3;
 constexpr uint32_t kCastF16toF32 = 4;
+// the block-scaled family starts at 16; 5..15 stay free for element-wise
+// casts and are unknown codes until one is defined
+constexpr uint32_t kCastF32toMX = 16;   // gather
+constexpr uint32_t kCastBF16toMX = 17;  // gather
+constexpr uint32_t kCastMXtoF32 = 18;   // scatter
+constexpr uint32_t kCastMXtoBF16 = 19;  // scatter
+constexpr uint32_t kMxBlock = 32;      // elements per scale byte
+
+constexpr bool is_mx_cast(uint32_t code) { return code >= kCastF32toMX; }
+// tensor-side element size of an mx descriptor
+constexpr uint32_t mx_elem_size(uint32_t code) {
+  return (code == kCastF32toMX || code == kCastMXtoF32) ? 4u : 2u;
+}
 
 // element classes of the non-finite scan (SCAN_* in ops/staging.py)
 constexpr uint32_t kScanF64 = 0;
@@ -141,7 +161,8 @@ inline std::vector<Desc> parse_descs(
       d.sizes[k] = (uint32_t)r[6 + k];
       d.strides[k] = (long long)r[12 + k];
     }
-    if (r[18] > kCastF16toF32) {
+    if (r[18] > kCastMXtoBF16 ||
+        (r[18] > kCastF16toF32 && r[18] < kCastF32toMX)) {
       throw std::runtime_error("unknown cast code in descriptor");
     }
     d.cast = (uint32_t)r[18];
@@ -151,9 +172,10 @@ inline std::vector<Desc> parse_descs(
 
 // Which entry point the descriptors are for.
 enum class DescKind {
-  Gather,   // pack_d2h: cast codes 0..2
+  Gather,   // pack_d2h: cast codes 0..2, and 16..17 (mx)
   Scatter,  // scatter_h2d: plain byte scatter, no cast code
-  Unpack,   // unpack_h2d: cast codes 0, 3, 4; needs a FlatSide
+  Unpack,   // unpack_h2d: cast codes 0, 3, 4, and 18..19 (mx); needs a
+            // FlatSide
   Scan,     // scan_nonfinite: no cast code; needs one class per descriptor
   Fingerprint,  // fingerprint_tensors: cast codes 0..2; flat_off is a hash
                 // offset and must be a multiple of vec
@@ -216,7 +238,8 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
     const bool cast = d.cast != kCastNone;
     switch (kind) {
       case DescKind::Gather:
-        if (d.cast > kCastF16) {
+        if (d.cast == kCastBF16toF32 || d.cast == kCastF16toF32 ||
+            d.cast > kCastBF16toMX) {
           refuse("widening cast descriptors are scatter-only (unpack_h2d)");
         }
         break;
@@ -225,7 +248,8 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
         if (cast) refuse("does not support cast descriptors");
         break;
       case DescKind::Unpack:
-        if (cast && d.cast <= kCastF16) {
+        if ((cast && d.cast <= kCastF16) || d.cast == kCastF32toMX ||
+            d.cast == kCastBF16toMX) {
           refuse("does not support narrowing cast descriptors");
         }
         break;
@@ -259,6 +283,41 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
       refuse("descriptor outside the payload");
     }
     const uint32_t v = d.vec;
+    if (is_mx_cast(d.cast)) {
+      // Block-scaled fp8: only Gather and Unpack let these codes through.
+      // The rules are the accesses mx_gather_* and mx_scatter_* make.
+      if (d.nbytes % kMxBlock != 0) refuse("mx: nbytes must be whole blocks");
+      if (v != 8 && v != 1) refuse("mx: vec must be 8 (aligned) or 1 (general)");
+      if (d.row_bytes == 0) refuse("mx: empty row");
+      unsigned long long n = d.row_bytes;
+      for (uint32_t k = 0; k < d.ndim; ++k) n *= d.sizes[k];
+      if ((n + kMxBlock - 1) / kMxBlock * kMxBlock != d.nbytes) {
+        refuse("mx: nbytes is not the block-padded element count");
+      }
+      // codes go as 8 B and 16 B accesses, scales as 16 B ones
+      if (d.flat_off % 16 != 0) refuse("mx: flat offset must be 16-aligned");
+      if (flat != nullptr) {
+        const uintptr_t base =
+            flat->slab_ptr != 0 ? flat->slab_ptr : flat->pinned_ptr;
+        if (base % 16 != 0) refuse("mx: flat side must be 16-aligned");
+        const unsigned long long stored =
+            (unsigned long long)d.nbytes + d.nbytes / kMxBlock;
+        if (d.flat_off > flat->total_bytes ||
+            stored > flat->total_bytes - d.flat_off) {
+          refuse("mx: scales region outside the slab");
+        }
+      }
+      if (v == 8 && d.ndim != 0 && d.row_bytes % kMxBlock != 0) {
+        refuse("mx: aligned class needs rows of 32k elements");
+      }
+      const unsigned long long align = v == 8 ? 16 : mx_elem_size(d.cast);
+      bool ok = reinterpret_cast<uintptr_t>(d.tensor_base) % align == 0;
+      for (uint32_t k = 0; k < d.ndim; ++k) {
+        ok = ok && (unsigned long long)d.strides[k] % align == 0;
+      }
+      if (!ok) refuse("mx: tensor side not aligned for its class");
+      continue;
+    }
     if (v != 16 && v != 8 && v != 4 && v != 2 && (v != 1 || cast)) {
       refuse(cast ? "cast descriptor: vec must be 16/8/4/2"
                   : "vec must be 16/8/4/2/1");

@@ -655,6 +655,517 @@ __global__ __launch_bounds__(kBlockThreads) void unpack_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// block-scaled fp8 (mxfp8_e4m3; docs/format.md): 32 elements share one
+// power-of-two scale byte X = E + 127 (E8M0), each element is one e4m3fn
+// code of x * 2^-E. A payload is [codes: 32*nb bytes][scales: nb bytes].
+// The descriptor's flat range is the codes region, one byte per element,
+// so a 64 KiB work unit is 2048 blocks and owns 2048 scale bytes at
+// flat_off + nbytes + s / 32.
+//
+//   - aligned class (vec 8: contiguous tensors, and rows of 32k elements
+//     with a 16 B aligned tensor side): lanes run across the unit, 8
+//     elements each: one 16 B load of bf16 or two of f32. The four lanes of
+//     a block reduce amax on the bit patterns (the order of non-negative
+//     floats is the order of their patterns) with two xor shuffles; a block
+//     never crosses a wave. Each lane converts its 8 elements and stores 8
+//     code bytes, 512 contiguous bytes per wave
+//   - general class (vec 1: every other layout): one lane per block; it
+//     walks the block's 32 elements, taking row_offset again at each row
+//     boundary, keeps them in a per-lane array and stores the codes as two
+//     16 B pieces
+//   - scales never leave as single bytes (in direct mode the flat side is
+//     pinned host memory across PCIe): the unit's scale bytes are collected
+//     in 2 KiB of LDS and, after a workgroup barrier, written as 16 B
+//     pieces; only the payload's last, short piece goes narrower. The
+//     scatter mirrors this: it first loads the unit's scales into LDS with
+//     16 B loads (the flat side is read exactly once), then decodes
+//   - conversion is integer arithmetic on the bit patterns, like the casts
+//     above: f32 subnormals, e4m3 subnormals and ties come out the same in
+//     every wave mode. A bf16 source is its f32 pattern (<< 16)
+//   - psum64: codes are hashed from the registers stored (or loaded), scales
+//     where they leave (enter) LDS, at their own payload offsets
+//   - the kernels below also run plain and cast descriptors, so a slab may
+//     mix all three; they are launched only for batches that hold an mx
+//     descriptor, and pack_kernel / unpack_kernel stay as they were
+// ---------------------------------------------------------------------------
+
+constexpr uint32_t kMxUnitBlocks = kWorkUnitBytes / kMxBlock;  // 2048
+
+// E of a block from the pattern of its amax (finite, sign cleared):
+// floor(log2 amax) - 8, one more when amax * 2^-E would exceed 448 =
+// 1.75 * 2^8, at least -127. Zero and f32 subnormals end at -127.
+__device__ __host__ inline int mx_block_exp(uint32_t amax) {
+  if (amax < 0x00800000u) return -127;
+  const int e = (int)(amax >> 23) - 135 + ((amax & 0x007FFFFFu) > 0x00600000u);
+  return e < -127 ? -127 : e;
+}
+
+// e4m3fn code of the f32 pattern u scaled by 2^-E, round to nearest even,
+// clamped to +-448; NaN and +-Inf become the NaN code with the sign kept.
+__device__ __host__ inline uint32_t mx_code(uint32_t u, int E) {
+  const uint32_t sign = (u >> 24) & 0x80u;
+  const uint32_t a = u & 0x7FFFFFFFu;
+  if (a >= 0x7F800000u) return sign | 0x7Fu;
+  if (a == 0u) return sign;
+  // |x| = M * 2^(ex - 23) with M in [2^23, 2^24)
+  uint32_t M = a & 0x007FFFFFu;
+  int ex = (int)(a >> 23) - 127;
+  if (a < 0x00800000u) {
+    const int lz = __builtin_clz(M) - 8;  // 1..23
+    M <<= lz;
+    ex = -126 - lz;
+  } else {
+    M |= 0x00800000u;
+  }
+  // y = |x| * 2^-E has exponent t. From t = -6 up it is an e4m3 normal with
+  // step 2^(t-3): q = RNE(M / 2^20) in [8, 16], and a carry to 16 runs into
+  // the exponent field. Below, the step stays 2^-9 (e4m3 subnormals).
+  const int t = ex - E;
+  const int shift = 20 + (t < -6 ? -6 - t : 0);
+  const uint32_t sh = shift > 26 ? 26u : (uint32_t)shift;  // >= 25 gives 0
+  const uint32_t q = (M + ((1u << (sh - 1)) - 1u) + ((M >> sh) & 1u)) >> sh;
+  const uint32_t code = t >= -6 ? ((uint32_t)(t + 6) << 3) + q : q;
+  return sign | (code > 0x7Eu ? 0x7Eu : code);
+}
+
+// f32 pattern of e4m3fn(code) * 2^(X - 127): exact, f32 subnormals included
+__device__ __host__ inline uint32_t mx_decode_bits(uint32_t c, uint32_t X) {
+  const uint32_t sign = (c & 0x80u) << 24;
+  const uint32_t a = c & 0x7Fu;
+  if (a == 0x7Fu || X == 0xFFu) return sign | 0x7FC00000u;
+  if (a == 0u) return sign;
+  const uint32_t ef = a >> 3, m = a & 7u;
+  int ex;
+  uint32_t frac;
+  if (ef != 0u) {
+    ex = (int)ef - 7;
+    frac = m << 20;
+  } else {
+    const int p = 31 - __builtin_clz(m);  // 0..2
+    ex = p - 9;
+    frac = (m << (23 - p)) & 0x007FFFFFu;
+  }
+  const int biased = ex + (int)X;  // ex + (X - 127) + 127
+  if (biased >= 255) return sign | 0x7F800000u;
+  if (biased > 0) return sign | ((uint32_t)biased << 23) | frac;
+  // only the top four bits of the significand are set and the shift is at
+  // most 10: nothing is lost
+  return sign | ((0x00800000u | frac) >> (1 - biased));
+}
+
+__device__ __forceinline__ unsigned long long psum_piece(
+    unsigned long long v, unsigned long long file_off) {
+  // a naturally aligned piece of at most 8 bytes, shifted into its word lane
+  return (v << (8 * (file_off & 7))) * psum_mult(file_off >> 3);
+}
+
+// 8 consecutive source elements as f32 patterns; the ones from `valid` on do
+// not exist and read as +0
+template <bool BF16>
+__device__ __forceinline__ void mx_load8(const char* src, uint32_t valid,
+                                         uint32_t (&v)[8]) {
+  if (valid >= 8) {
+    const uint4 a = *reinterpret_cast<const uint4*>(src);
+    if (BF16) {
+      v[0] = a.x << 16; v[1] = a.x & 0xFFFF0000u;
+      v[2] = a.y << 16; v[3] = a.y & 0xFFFF0000u;
+      v[4] = a.z << 16; v[5] = a.z & 0xFFFF0000u;
+      v[6] = a.w << 16; v[7] = a.w & 0xFFFF0000u;
+    } else {
+      const uint4 b = *reinterpret_cast<const uint4*>(src + 16);
+      v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+      v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    }
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) {
+      v[k] = 0u;
+      if (k < valid) {
+        v[k] = BF16 ? (uint32_t)reinterpret_cast<const uint16_t*>(src)[k] << 16
+                    : reinterpret_cast<const uint32_t*>(src)[k];
+      }
+    }
+  }
+}
+
+// amax pattern of one element: non-finite elements do not exist for it
+__device__ __forceinline__ uint32_t mx_amax_of(uint32_t u) {
+  const uint32_t a = u & 0x7FFFFFFFu;
+  return a < 0x7F800000u ? a : 0u;
+}
+
+__device__ __forceinline__ uint32_t mx_code4(const uint32_t* v, int E) {
+  return mx_code(v[0], E) | (mx_code(v[1], E) << 8) | (mx_code(v[2], E) << 16) |
+         (mx_code(v[3], E) << 24);
+}
+
+// where element i of an aligned-class tensor sits, and how many of the 8
+// elements from it on exist
+template <int TS>
+__device__ __forceinline__ const char* mx_aligned_addr(const Desc& d,
+                                                       uint32_t i,
+                                                       uint32_t& valid) {
+  if (d.ndim == 0) {
+    const uint32_t n = d.row_bytes;
+    valid = i < n ? n - i : 0u;
+    return d.tensor_base + (unsigned long long)TS * i;
+  }
+  // rows of 32k elements tile the codes region: every element exists
+  const uint32_t row = i / d.row_bytes;
+  const uint32_t col = i - row * d.row_bytes;
+  valid = 8u;
+  return d.tensor_base + row_offset(d, row) + (unsigned long long)TS * col;
+}
+
+// Aligned gather of [s, e) of the codes region of one work unit; the unit's
+// scale bytes go to `lds`.
+template <bool BF16, bool HASH>
+__device__ unsigned long long mx_gather_aligned(const Desc& d, char* flat_base,
+                                                uint32_t s, uint32_t e,
+                                                unsigned char* lds) {
+  char* flat = flat_base + d.flat_off;
+  unsigned long long h = 0;
+  for (uint32_t i = s + threadIdx.x * 8; i < e; i += kBlockThreads * 8) {
+    uint32_t valid;
+    const char* src = mx_aligned_addr<BF16 ? 2 : 4>(d, i, valid);
+    uint32_t v[8];
+    mx_load8<BF16>(src, valid, v);
+    uint32_t amax = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) amax = max(amax, mx_amax_of(v[k]));
+    // e and the unit are whole blocks: the four lanes of a block are all
+    // here or all gone
+    amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
+    amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2, 64));
+    const int E = mx_block_exp(amax);
+    const uint2 o = make_uint2(mx_code4(v, E), mx_code4(v + 4, E));
+    *reinterpret_cast<uint2*>(flat + i) = o;
+    if (HASH) {
+      h += (((unsigned long long)o.y << 32) | o.x) *
+           psum_mult((d.flat_off + i) >> 3);
+    }
+    if ((threadIdx.x & 3u) == 0u) lds[(i - s) >> 5] = (unsigned char)(E + 127);
+  }
+  return h;
+}
+
+// number of elements of a general-class tensor
+__device__ __forceinline__ uint32_t mx_numel(const Desc& d) {
+  uint32_t n = d.row_bytes;
+  for (uint32_t k = 0; k < d.ndim; ++k) n *= d.sizes[k];
+  return n;
+}
+
+// General gather: one lane per block, walking rows.
+template <bool BF16, bool HASH>
+__device__ unsigned long long mx_gather_general(const Desc& d, char* flat_base,
+                                                uint32_t s, uint32_t e,
+                                                unsigned char* lds) {
+  constexpr int TS = BF16 ? 2 : 4;
+  char* flat = flat_base + d.flat_off;
+  const uint32_t rb = d.row_bytes;
+  const uint32_t n = mx_numel(d);
+  unsigned long long h = 0;
+  for (uint32_t i0 = s + threadIdx.x * kMxBlock; i0 < e;
+       i0 += kBlockThreads * kMxBlock) {
+    uint32_t row = i0 / rb;
+    uint32_t col = i0 - row * rb;
+    const char* p = d.tensor_base + row_offset(d, row);
+    uint32_t v[kMxBlock];
+    uint32_t amax = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kMxBlock; ++j) {
+      v[j] = 0u;
+      if (i0 + j < n) {
+        const char* q = p + (unsigned long long)TS * col;
+        v[j] = BF16 ? (uint32_t)*reinterpret_cast<const uint16_t*>(q) << 16
+                    : *reinterpret_cast<const uint32_t*>(q);
+        if (++col == rb && i0 + j + 1 < n) {
+          col = 0;
+          p = d.tensor_base + row_offset(d, ++row);
+        }
+      }
+      amax = max(amax, mx_amax_of(v[j]));
+    }
+    const int E = mx_block_exp(amax);
+    const uint4 a = make_uint4(mx_code4(v, E), mx_code4(v + 4, E),
+                               mx_code4(v + 8, E), mx_code4(v + 12, E));
+    const uint4 b = make_uint4(mx_code4(v + 16, E), mx_code4(v + 20, E),
+                               mx_code4(v + 24, E), mx_code4(v + 28, E));
+    *reinterpret_cast<uint4*>(flat + i0) = a;
+    *reinterpret_cast<uint4*>(flat + i0 + 16) = b;
+    if (HASH) {
+      h += psum_regs<16>(a, d.flat_off + i0) +
+           psum_regs<16>(b, d.flat_off + i0 + 16);
+    }
+    lds[(i0 - s) >> 5] = (unsigned char)(E + 127);
+  }
+  return h;
+}
+
+// Move one unit's `count` scale bytes between LDS and the payload (TO_FLAT:
+// out of LDS after the gather filled it; else into LDS before the scatter
+// reads it), as 16 B pieces; only a payload's last piece is cut into
+// naturally aligned 8 / 4 / 2 / 1 B ones. `payload` is 16 B aligned
+// (check_descs). When HASH, returns the psum64 contribution of the bytes
+// moved. Both barriers are reached by the whole workgroup: the owner, the
+// cast code and the unit are uniform across it.
+template <bool TO_FLAT, bool HASH>
+__device__ unsigned long long mx_move_scales(char* payload, unsigned char* lds,
+                                             uint32_t count,
+                                             unsigned long long file_off) {
+  unsigned long long h = 0;
+  __syncthreads();
+  const uint32_t wide = count >> 4;
+  if (threadIdx.x < wide) {
+    uint4* src = reinterpret_cast<uint4*>(TO_FLAT ? (char*)lds : payload);
+    uint4* dst = reinterpret_cast<uint4*>(TO_FLAT ? payload : (char*)lds);
+    const uint4 a = src[threadIdx.x];
+    dst[threadIdx.x] = a;
+    if (HASH) h += psum_regs<16>(a, file_off + 16ull * threadIdx.x);
+  }
+  if (threadIdx.x == 0) {
+    uint32_t p = wide << 4;
+#pragma unroll
+    for (uint32_t w = 8; w >= 1; w >>= 1) {
+      if (count - p < w) continue;
+      char* src = (TO_FLAT ? (char*)lds : payload) + p;
+      char* dst = (TO_FLAT ? payload : (char*)lds) + p;
+      unsigned long long a;
+      if (w == 8) {
+        a = *reinterpret_cast<unsigned long long*>(src);
+        *reinterpret_cast<unsigned long long*>(dst) = a;
+      } else if (w == 4) {
+        a = *reinterpret_cast<uint32_t*>(src);
+        *reinterpret_cast<uint32_t*>(dst) = (uint32_t)a;
+      } else if (w == 2) {
+        a = *reinterpret_cast<uint16_t*>(src);
+        *reinterpret_cast<uint16_t*>(dst) = (uint16_t)a;
+      } else {
+        a = *reinterpret_cast<unsigned char*>(src);
+        *reinterpret_cast<unsigned char*>(dst) = (unsigned char)a;
+      }
+      if (HASH) h += psum_piece(a, file_off + p);
+      p += w;
+    }
+  }
+  __syncthreads();
+  return h;
+}
+
+// One mx descriptor's work unit of the gather: codes, then the scales.
+template <bool HASH>
+__device__ unsigned long long mx_gather_unit(const Desc& d, char* flat_base,
+                                             uint32_t s, uint32_t e,
+                                             unsigned char* lds) {
+  const bool bf16 = d.cast == kCastBF16toMX;
+  unsigned long long h;
+  if (d.vec == 8) {
+    h = bf16 ? mx_gather_aligned<true, HASH>(d, flat_base, s, e, lds)
+             : mx_gather_aligned<false, HASH>(d, flat_base, s, e, lds);
+  } else {
+    h = bf16 ? mx_gather_general<true, HASH>(d, flat_base, s, e, lds)
+             : mx_gather_general<false, HASH>(d, flat_base, s, e, lds);
+  }
+  const unsigned long long scales_off = d.flat_off + d.nbytes + (s >> 5);
+  return h + mx_move_scales<true, HASH>(flat_base + scales_off, lds,
+                                        (e - s) >> 5, scales_off);
+}
+
+// pack_kernel for batches that hold an mx descriptor; plain and cast
+// descriptors of the same slab take pack_kernel's own routes.
+template <bool HASH>
+__global__ __launch_bounds__(kBlockThreads) void pack_mx_kernel(
+    const Desc* __restrict__ descs, int n,
+    const unsigned long long* __restrict__ wu_prefix,
+    unsigned long long total_wus, char* __restrict__ flat_base,
+    unsigned long long* __restrict__ hash_out) {
+  __shared__ uint4 lds_scales[kMxUnitBlocks / 16];
+  unsigned char* lds = reinterpret_cast<unsigned char*>(lds_scales);
+  for_each_work_unit(
+      descs, n, wu_prefix, total_wus,
+      [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
+        unsigned long long h = 0;
+        if (is_mx_cast(d.cast)) {
+          h = mx_gather_unit<HASH>(d, flat_base, s, e, lds);
+        } else if (d.cast != kCastNone) {
+          switch (d.vec) {
+            case 16: h = cast_range<16, HASH>(d, flat_base, s, e); break;
+            case 8: h = cast_range<8, HASH>(d, flat_base, s, e); break;
+            case 4: h = cast_range<4, HASH>(d, flat_base, s, e); break;
+            default: h = cast_range<2, HASH>(d, flat_base, s, e); break;
+          }
+        } else {
+          switch (d.vec) {
+            case 16: h = gather_range<16, HASH>(d, flat_base, s, e); break;
+            case 8: h = gather_range<8, HASH>(d, flat_base, s, e); break;
+            case 4: h = gather_range<4, HASH>(d, flat_base, s, e); break;
+            case 2: h = gather_range<2, HASH>(d, flat_base, s, e); break;
+            default: h = gather_range<1, HASH>(d, flat_base, s, e); break;
+          }
+        }
+        if (HASH) add_per_wave(&hash_out[owner], h);
+      });
+}
+
+// the decoded element as the target stores it: an f32 pattern, or its bf16
+// rounding (to nearest even) in the low half
+template <bool BF16>
+__device__ __forceinline__ uint32_t mx_out(uint32_t code, uint32_t X) {
+  const uint32_t f = mx_decode_bits(code, X);
+  return BF16 ? (f32_to_bf16_bits(f) & 0xFFFFu) : f;
+}
+
+// Aligned scatter of [s, e) of the codes region; the unit's scales are in
+// `lds` already.
+template <bool BF16, bool HASH>
+__device__ unsigned long long mx_scatter_aligned(const Desc& d,
+                                                 const char* flat_base,
+                                                 uint32_t s, uint32_t e,
+                                                 unsigned long long hash_off,
+                                                 const unsigned char* lds) {
+  const char* flat = flat_base + d.flat_off;
+  unsigned long long h = 0;
+  for (uint32_t i = s + threadIdx.x * 8; i < e; i += kBlockThreads * 8) {
+    const uint2 c = *reinterpret_cast<const uint2*>(flat + i);
+    if (HASH) {
+      h += (((unsigned long long)c.y << 32) | c.x) *
+           psum_mult((hash_off + i) >> 3);
+    }
+    const uint32_t X = lds[(i - s) >> 5];
+    uint32_t valid;
+    char* dst = const_cast<char*>(mx_aligned_addr<BF16 ? 2 : 4>(d, i, valid));
+    uint32_t o[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      o[k] = mx_out<BF16>(((k < 4 ? c.x : c.y) >> (8 * (k & 3))) & 0xFFu, X);
+    }
+    if (valid >= 8) {
+      if (BF16) {
+        *reinterpret_cast<uint4*>(dst) =
+            make_uint4(o[0] | (o[1] << 16), o[2] | (o[3] << 16),
+                       o[4] | (o[5] << 16), o[6] | (o[7] << 16));
+      } else {
+        *reinterpret_cast<uint4*>(dst) = make_uint4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<uint4*>(dst + 16) = make_uint4(o[4], o[5], o[6], o[7]);
+      }
+    } else {
+#pragma unroll
+      for (uint32_t k = 0; k < 8; ++k) {
+        if (k < valid) {
+          if (BF16) reinterpret_cast<uint16_t*>(dst)[k] = (uint16_t)o[k];
+          else reinterpret_cast<uint32_t*>(dst)[k] = o[k];
+        }
+      }
+    }
+  }
+  return h;
+}
+
+// General scatter: one lane per block, walking rows.
+template <bool BF16, bool HASH>
+__device__ unsigned long long mx_scatter_general(const Desc& d,
+                                                 const char* flat_base,
+                                                 uint32_t s, uint32_t e,
+                                                 unsigned long long hash_off,
+                                                 const unsigned char* lds) {
+  constexpr int TS = BF16 ? 2 : 4;
+  const char* flat = flat_base + d.flat_off;
+  char* base = const_cast<char*>(d.tensor_base);
+  const uint32_t rb = d.row_bytes;
+  const uint32_t n = mx_numel(d);
+  unsigned long long h = 0;
+  for (uint32_t i0 = s + threadIdx.x * kMxBlock; i0 < e;
+       i0 += kBlockThreads * kMxBlock) {
+    const uint4 a = *reinterpret_cast<const uint4*>(flat + i0);
+    const uint4 b = *reinterpret_cast<const uint4*>(flat + i0 + 16);
+    if (HASH) {
+      h += psum_regs<16>(a, hash_off + i0) + psum_regs<16>(b, hash_off + i0 + 16);
+    }
+    const uint32_t c[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    const uint32_t X = lds[(i0 - s) >> 5];
+    uint32_t row = i0 / rb;
+    uint32_t col = i0 - row * rb;
+    char* p = base + row_offset(d, row);
+#pragma unroll
+    for (uint32_t j = 0; j < kMxBlock; ++j) {
+      if (i0 + j < n) {
+        const uint32_t o = mx_out<BF16>((c[j >> 2] >> (8 * (j & 3))) & 0xFFu, X);
+        char* q = p + (unsigned long long)TS * col;
+        if (BF16) *reinterpret_cast<uint16_t*>(q) = (uint16_t)o;
+        else *reinterpret_cast<uint32_t*>(q) = o;
+        if (++col == rb && i0 + j + 1 < n) {
+          col = 0;
+          p = base + row_offset(d, ++row);
+        }
+      }
+    }
+  }
+  return h;
+}
+
+// One mx descriptor's work unit of the scatter: the scales, then the codes.
+template <bool HASH>
+__device__ unsigned long long mx_scatter_unit(const Desc& d,
+                                              const char* flat_base, uint32_t s,
+                                              uint32_t e,
+                                              unsigned long long hash_off,
+                                              unsigned char* lds) {
+  const unsigned long long scales_off =
+      (unsigned long long)d.nbytes + (s >> 5);
+  unsigned long long h = mx_move_scales<false, HASH>(
+      const_cast<char*>(flat_base) + d.flat_off + scales_off, lds, (e - s) >> 5,
+      hash_off + scales_off);
+  const bool bf16 = d.cast == kCastMXtoBF16;
+  if (d.vec == 8) {
+    h += bf16 ? mx_scatter_aligned<true, HASH>(d, flat_base, s, e, hash_off, lds)
+              : mx_scatter_aligned<false, HASH>(d, flat_base, s, e, hash_off, lds);
+  } else {
+    h += bf16 ? mx_scatter_general<true, HASH>(d, flat_base, s, e, hash_off, lds)
+              : mx_scatter_general<false, HASH>(d, flat_base, s, e, hash_off, lds);
+  }
+  return h;
+}
+
+// unpack_kernel for batches that hold an mx descriptor
+template <bool HASH>
+__global__ __launch_bounds__(kBlockThreads) void unpack_mx_kernel(
+    const Desc* __restrict__ descs, int n,
+    const unsigned long long* __restrict__ wu_prefix,
+    unsigned long long total_wus, const char* __restrict__ flat_base,
+    unsigned long long* __restrict__ hash_out,
+    unsigned long long hash_byte0) {
+  __shared__ uint4 lds_scales[kMxUnitBlocks / 16];
+  unsigned char* lds = reinterpret_cast<unsigned char*>(lds_scales);
+  for_each_work_unit(
+      descs, n, wu_prefix, total_wus,
+      [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
+        const unsigned long long ho = hash_byte0 + d.flat_off;
+        const char* fb = flat_base;
+        unsigned long long h = 0;
+        if (is_mx_cast(d.cast)) {
+          h = mx_scatter_unit<HASH>(d, fb, s, e, ho, lds);
+        } else if (d.cast != kCastNone) {
+          switch (d.vec) {
+            case 16: h = widen_range<16, HASH>(d, fb, s, e, ho); break;
+            case 8: h = widen_range<8, HASH>(d, fb, s, e, ho); break;
+            case 4: h = widen_range<4, HASH>(d, fb, s, e, ho); break;
+            default: h = widen_range<2, HASH>(d, fb, s, e, ho); break;
+          }
+        } else {
+          switch (d.vec) {
+            case 16: h = scatter_range<16, HASH>(d, fb, s, e, ho); break;
+            case 8: h = scatter_range<8, HASH>(d, fb, s, e, ho); break;
+            case 4: h = scatter_range<4, HASH>(d, fb, s, e, ho); break;
+            case 2: h = scatter_range<2, HASH>(d, fb, s, e, ho); break;
+            default: h = scatter_range<1, HASH>(d, fb, s, e, ho); break;
+          }
+        }
+        if (HASH) add_per_wave(&hash_out[owner], h);
+      });
+}
+
+// ---------------------------------------------------------------------------
 // non-finite scan: count NaN and +-Inf elements per descriptor, read-only.
 // Same descriptors, driver and traversal as the gather; there is no flat
 // side (flat_off is unused) and nbytes/row_bytes/vec are the tensor's own
@@ -1999,8 +2510,11 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
   const FlatSide flat_side{slab_ptr, pinned_ptr, total_bytes, hash_byte0};
   check_descs(descs, kind, &flat_side);
   const bool gather = kind == DescKind::Gather;
-  bool any_cast = false;
-  for (const Desc& d : descs) any_cast = any_cast || d.cast != kCastNone;
+  bool any_cast = false, any_mx = false;
+  for (const Desc& d : descs) {
+    any_cast = any_cast || d.cast != kCastNone;
+    any_mx = any_mx || is_mx_cast(d.cast);
+  }
 
   HIP_CHECK(hipSetDevice(device));
   DeviceCtx& ctx = get_ctx(device);
@@ -2054,17 +2568,21 @@ long long launch_pack(const std::vector<unsigned long long>& flat, int n,
                                total_bytes, hipMemcpyHostToDevice, stream));
     }
     if (gather) {
-      auto kernel = any_cast ? (hash ? pack_kernel<true, true>
-                                     : pack_kernel<false, true>)
-                             : (hash ? pack_kernel<true, false>
-                                     : pack_kernel<false, false>);
+      auto kernel = any_mx     ? (hash ? pack_mx_kernel<true>
+                                       : pack_mx_kernel<false>)
+                    : any_cast ? (hash ? pack_kernel<true, true>
+                                       : pack_kernel<false, true>)
+                               : (hash ? pack_kernel<true, false>
+                                       : pack_kernel<false, false>);
       hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
                          d_descs, n, d_prefix, total_wus, flat_base, hash_out);
     } else {
-      auto kernel = any_cast ? (hash ? unpack_kernel<true, true>
-                                     : unpack_kernel<false, true>)
-                             : (hash ? unpack_kernel<true, false>
-                                     : unpack_kernel<false, false>);
+      auto kernel = any_mx     ? (hash ? unpack_mx_kernel<true>
+                                       : unpack_mx_kernel<false>)
+                    : any_cast ? (hash ? unpack_kernel<true, true>
+                                       : unpack_kernel<false, true>)
+                               : (hash ? unpack_kernel<true, false>
+                                       : unpack_kernel<false, false>);
       hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, stream,
                          d_descs, n, d_prefix, total_wus,
                          static_cast<const char*>(flat_base), hash_out,

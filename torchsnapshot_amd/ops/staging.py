@@ -33,6 +33,7 @@ from typing import Any, Callable, Dict, Iterator, List, Optional, Sequence, Tupl
 import torch
 
 from .. import knobs
+from ..serialization import MXFP8_E4M3
 
 ALIGN = 256  # slab alignment per packed tensor
 
@@ -128,18 +129,48 @@ class PackItem:
     # 2*vec source bytes per vec stored bytes.
     cast: int = 0
 
+    @property
+    def stored_bytes(self) -> int:
+        """Payload bytes in the slab: ``nbytes``, and for a block-scaled
+        item the scale bytes that follow the codes region."""
+        if self.cast >= CAST_F32_TO_MX:
+            return self.nbytes + self.nbytes // MX_BLOCK
+        return self.nbytes
+
 
 CAST_NONE = 0
 CAST_F32_TO_BF16 = 1
 CAST_F32_TO_F16 = 2
 
+# Block-scaled fp8 (docs/format.md). It is no torch dtype: wherever a stored
+# dtype is named, this string stands for it.
+MX_BLOCK = 32
+CAST_F32_TO_MX = 16
+CAST_BF16_TO_MX = 17
+
+StoredDtype = Any  # a torch.dtype, or MXFP8_E4M3
+
 _CAST_CODES = {
     (torch.float32, torch.bfloat16): CAST_F32_TO_BF16,
     (torch.float32, torch.float16): CAST_F32_TO_F16,
+    (torch.float32, MXFP8_E4M3): CAST_F32_TO_MX,
+    (torch.bfloat16, MXFP8_E4M3): CAST_BF16_TO_MX,
 }
 
 
-def cast_code(src: torch.dtype, dst: Optional[torch.dtype]) -> int:
+def is_mx(dtype: Any) -> bool:
+    return isinstance(dtype, str) and dtype == MXFP8_E4M3
+
+
+def stored_nbytes(numel: int, dtype: StoredDtype) -> int:
+    """Payload bytes of ``numel`` elements stored as ``dtype``: 33 bytes per
+    block of 32 for block-scaled fp8."""
+    if is_mx(dtype):
+        return 33 * ((numel + MX_BLOCK - 1) // MX_BLOCK)
+    return numel * dtype.itemsize
+
+
+def cast_code(src: torch.dtype, dst: Optional[StoredDtype]) -> int:
     """Descriptor cast code for storing a ``src``-typed tensor as ``dst``.
     An unsupported pair raises: a tensor is never silently left uncast."""
     if dst is None or dst == src:
@@ -148,23 +179,79 @@ def cast_code(src: torch.dtype, dst: Optional[torch.dtype]) -> int:
     if code is None:
         raise ValueError(
             f"the gather kernel cannot cast {src} to {dst}; supported: "
-            "float32 -> bfloat16, float32 -> float16"
+            "float32 -> bfloat16, float32 -> float16, float32 or bfloat16 "
+            f"-> {MXFP8_E4M3!r}"
         )
     return code
+
+
+def _pow2(k: torch.Tensor) -> torch.Tensor:
+    """2^k in float64 for an int64 tensor with |k| < 1023, built from the
+    bit pattern: exact on every device."""
+    return ((k + 1023) << 52).view(torch.float64)
+
+
+def mx_encode(t: torch.Tensor) -> torch.Tensor:
+    """The mxfp8_e4m3 payload of ``t`` (float32 or bfloat16, any layout) as
+    a uint8 tensor on ``t``'s device: 32 code bytes per block of its
+    row-major elements, then one scale byte per block (docs/format.md). The
+    torch expression of what the gather kernel stores, byte for byte."""
+    x = resolve_lazy(t.detach()).reshape(-1).to(torch.float64)
+    n = x.numel()
+    nb = (n + MX_BLOCK - 1) // MX_BLOCK
+    if n != nb * MX_BLOCK:
+        x = torch.cat([x, x.new_zeros(nb * MX_BLOCK - n)])
+    x = x.reshape(nb, MX_BLOCK)
+    finite = torch.isfinite(x)
+    amax = torch.where(finite, x.abs(), 0.0).amax(dim=1)
+    # amax = m * 2^e with m in [0.5, 1): floor(log2 amax) is e - 1
+    exp = torch.frexp(amax).exponent.to(torch.int64) - 9
+    exp = exp + (amax * _pow2(-exp) > 448.0).to(torch.int64)
+    exp = torch.where(amax == 0, -127, exp).clamp_(min=-127)
+    y = (torch.where(finite, x, 0.0) * _pow2(-exp)[:, None]).clamp_(-448.0, 448.0)
+    codes = y.to(torch.float32).to(torch.float8_e4m3fn).view(torch.uint8)
+    nan_code = torch.signbit(x).to(torch.uint8) * 0x80 + 0x7F
+    codes = torch.where(finite, codes, nan_code)
+    return torch.cat([codes.reshape(-1), (exp + 127).to(torch.uint8)])
+
+
+def mx_decode(payload: torch.Tensor, n: int, dtype: torch.dtype) -> torch.Tensor:
+    """The ``n`` elements of an mxfp8_e4m3 ``payload`` (uint8, 33 bytes per
+    block) as a 1-D ``dtype`` tensor on its device: code times 2^(X - 127),
+    exact in float32, then rounded to ``dtype``; a scale byte of 0xFF gives
+    NaN. The torch expression of what the scatter kernel restores."""
+    nb = (n + MX_BLOCK - 1) // MX_BLOCK
+    if payload.numel() != 33 * nb:
+        raise ValueError(
+            f"mxfp8_e4m3 payload of {n} elements must be {33 * nb} bytes, "
+            f"got {payload.numel()}"
+        )
+    codes = payload[: MX_BLOCK * nb].view(torch.float8_e4m3fn).to(torch.float32)
+    scale = payload[MX_BLOCK * nb :].to(torch.int64) - 127
+    x = codes.to(torch.float64).reshape(nb, MX_BLOCK) * _pow2(scale)[:, None]
+    # the MX rule: a scale byte of 0xFF makes the whole block NaN
+    x = torch.where((scale == 128)[:, None], float("nan"), x)
+    return x.reshape(-1)[:n].to(torch.float32).to(dtype)
 
 
 # widening on restore (scatter only): the descriptor convention is the cast
 # one, flat side in stored 2-byte units and tensor side in float32 bytes
 CAST_BF16_TO_F32 = 3
 CAST_F16_TO_F32 = 4
+# decoding block-scaled fp8: flat side in code bytes, tensor side in target
+# bytes
+CAST_MX_TO_F32 = 18
+CAST_MX_TO_BF16 = 19
 
 _WIDEN_CODES = {
     (torch.bfloat16, torch.float32): CAST_BF16_TO_F32,
     (torch.float16, torch.float32): CAST_F16_TO_F32,
+    (MXFP8_E4M3, torch.float32): CAST_MX_TO_F32,
+    (MXFP8_E4M3, torch.bfloat16): CAST_MX_TO_BF16,
 }
 
 
-def widen_code(stored: torch.dtype, target: torch.dtype) -> int:
+def widen_code(stored: StoredDtype, target: torch.dtype) -> int:
     """Descriptor cast code for restoring ``stored``-typed bytes into a
     ``target``-typed tensor. An unsupported pair raises."""
     if stored == target:
@@ -173,7 +260,8 @@ def widen_code(stored: torch.dtype, target: torch.dtype) -> int:
     if code is None:
         raise ValueError(
             f"the scatter kernel cannot restore {stored} into {target}; "
-            "supported: equal dtypes, bfloat16 -> float32, float16 -> float32"
+            "supported: equal dtypes, bfloat16 -> float32, float16 -> float32, "
+            f"{MXFP8_E4M3!r} -> float32 or bfloat16"
         )
     return code
 
@@ -255,7 +343,7 @@ def build_pack_items(
             item = _build_cast_item(t, out_dtype, cast, off)
             items.append(item)
             offsets.append(off)
-            off += (item.nbytes + ALIGN - 1) // ALIGN * ALIGN
+            off += (item.stored_bytes + ALIGN - 1) // ALIGN * ALIGN
             continue
         nbytes = t.numel() * t.element_size()
         sizes, strides = collapse_layout(t)
@@ -293,6 +381,8 @@ def _build_cast_item(
     (two 16 B loads at vec 16, else one load of 2*vec)."""
     if t.numel() == 0:
         return PackItem(t.data_ptr(), off, 0, 0, [], [], 1, CAST_NONE)
+    if is_mx(out_dtype):
+        return _build_mx_item(t, cast, off)
     src_esz = t.element_size()
     dst_esz = out_dtype.itemsize
     sizes, strides = collapse_layout(t)
@@ -313,6 +403,37 @@ def _build_cast_item(
         outer_sizes=outer_sizes,
         outer_strides=outer_strides_b,
         vec=vec,
+        cast=cast,
+    )
+
+
+def _build_mx_item(t: torch.Tensor, cast: int, off: int) -> PackItem:
+    """Descriptor of a tensor stored as, or restored from, block-scaled fp8.
+    The flat side is one code byte per element: ``nbytes`` is the codes
+    region, 32 bytes per block, and ``row_bytes`` the innermost run in
+    elements. ``vec`` names the kernel class: 8, four lanes per block with
+    16-byte tensor-side accesses, for a contiguous tensor or rows of 32k
+    elements whose base and strides are 16-byte aligned; 1, one lane per
+    block, for every other layout."""
+    esz = t.element_size()
+    sizes, strides = collapse_layout(t)
+    row_elems, outer_sizes, outer_strides_b, src_align = _layout_rows(
+        sizes, strides, esz, 1, t.data_ptr()
+    )
+    if src_align < esz:
+        raise ValueError(
+            f"cannot stage a {t.dtype} tensor as {MXFP8_E4M3} whose address or "
+            f"strides are not {esz}-byte aligned"
+        )
+    aligned = src_align == 16 and (not outer_sizes or row_elems % MX_BLOCK == 0)
+    return PackItem(
+        src_ptr=t.data_ptr(),
+        flat_offset=off,
+        nbytes=(t.numel() + MX_BLOCK - 1) // MX_BLOCK * MX_BLOCK,
+        row_bytes=row_elems,
+        outer_sizes=outer_sizes,
+        outer_strides=outer_strides_b,
+        vec=8 if aligned else 1,
         cast=cast,
     )
 
@@ -338,7 +459,14 @@ def build_scatter_items(
         else:
             it = build_pack_items([t])[0][0]
             it.flat_offset = off
-        if it.nbytes:
+        if it.nbytes and is_mx(stored):
+            # codes and scales move as 16-byte pieces; vec names the class
+            if (flat_base + off) % 16:
+                raise ValueError(
+                    f"cannot decode {MXFP8_E4M3} from a payload at address "
+                    f"{flat_base + off:#x}: not 16-byte aligned"
+                )
+        elif it.nbytes:
             it.vec = math.gcd(it.vec, flat_base + off)
             if it.cast != CAST_NONE and it.vec < 2:
                 raise ValueError(
@@ -389,7 +517,7 @@ def _scatter_layout_plan(
         return None
     if outer_dim_count(target) > MAX_OUTER_DIMS:
         return None
-    if target.numel() * stored_dtype.itemsize >= _KERNEL_MAX_BYTES:
+    if stored_nbytes(target.numel(), stored_dtype) >= _KERNEL_MAX_BYTES:
         return None
     # torch strides are whole elements, so the base address decides whether
     # every element is aligned
@@ -408,7 +536,7 @@ def scatter_member(
         knobs.get_restore_mode() == "torch"
         or not HIP_EXT_AVAILABLE
         or knobs.is_hip_staging_disabled()
-        or flat_offset % stored_dtype.itemsize
+        or flat_offset % (16 if is_mx(stored_dtype) else stored_dtype.itemsize)
         or scatter_plan(target, stored_dtype) is None
     ):
         return None
@@ -1323,7 +1451,7 @@ class StagingEngine:
             for t in tensors
         ]
         items, offsets, total = build_pack_items(tensors, out_dtypes)
-        nbytes_list = [it.nbytes for it in items]
+        nbytes_list = [it.stored_bytes for it in items]
         pinned = get_pinned_pool().acquire(max(total, 1))
         batch = StagedBatch(
             pinned=pinned,
@@ -1406,7 +1534,7 @@ class StagingEngine:
                     for it in items:
                         if it.flat_offset > prev_end:
                             pin_np[prev_end : it.flat_offset] = 0
-                        prev_end = it.flat_offset + it.nbytes
+                        prev_end = it.flat_offset + it.stored_bytes
                     if total > prev_end:
                         pin_np[prev_end:total] = 0
                 handle = _csnap.pack_d2h(
@@ -1778,10 +1906,15 @@ class StagingEngine:
         for t, it, out_dtype in zip(tensors, items, out_dtypes):
             if it.nbytes == 0:
                 continue
-            if it.cast != CAST_NONE:
-                t = t.to(out_dtype)
-            flat = t.contiguous().reshape(-1).view(torch.uint8)
-            dst = batch.pinned.tensor[it.flat_offset : it.flat_offset + it.nbytes]
+            if is_mx(out_dtype):
+                flat = mx_encode(t)
+            else:
+                if it.cast != CAST_NONE:
+                    t = t.to(out_dtype)
+                flat = t.contiguous().reshape(-1).view(torch.uint8)
+            dst = batch.pinned.tensor[
+                it.flat_offset : it.flat_offset + it.stored_bytes
+            ]
             dst.copy_(flat, non_blocking=True)
         torch.cuda.synchronize(self.device)
         batch._done = True

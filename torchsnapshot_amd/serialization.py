@@ -13,7 +13,7 @@ Two serializers (parity with reference torchsnapshot/serialization.py):
 from __future__ import annotations
 
 import io
-from typing import Tuple
+from typing import Any, Tuple
 
 import torch
 
@@ -50,8 +50,23 @@ for _name in (
 _QUANTIZED_DTYPES = [torch.qint8, torch.quint8, torch.qint32]
 
 
-def dtype_to_str(dtype: torch.dtype) -> str:
+# block-scaled fp8 (docs/format.md): a stored format, not a torch dtype. It
+# is named by this string in save_dtype and in the manifest
+MXFP8_E4M3 = "mxfp8_e4m3"
+
+
+def dtype_to_str(dtype: Any) -> str:
+    if dtype == MXFP8_E4M3:
+        return MXFP8_E4M3
     return str(dtype).removeprefix("torch.")
+
+
+def entry_tensor_dtype(entry: Any) -> torch.dtype:
+    """The dtype of the tensor a tensor or chunked entry holds: the logical
+    one when the payload is block-scaled fp8."""
+    return str_to_dtype(
+        entry.logical_dtype if entry.dtype == MXFP8_E4M3 else entry.dtype
+    )
 
 
 STR_TO_DTYPE = {dtype_to_str(d): d for d in _ALL_DTYPES + _QUANTIZED_DTYPES}

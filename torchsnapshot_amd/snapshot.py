@@ -66,6 +66,7 @@ from .manifest_ops import (
     get_manifest_for_rank,
     handle_sharded_tensor_elasticity,
 )
+from .serialization import MXFP8_E4M3
 from .partitioner import PartitionItem, partition_write_reqs
 from .pg_wrapper import PGWrapper
 from .rng_state import RNGState
@@ -112,9 +113,9 @@ def _match_segments(segs: List[str], pats: List[str]) -> bool:
 # save_dtype: narrowing policy for float32 leaves
 # ---------------------------------------------------------------------------
 
-SaveDtype = Union[None, torch.dtype, Dict[str, torch.dtype]]
+SaveDtype = Union[None, torch.dtype, str, Dict[str, Union[torch.dtype, str]]]
 
-_SAVE_DTYPE_TARGETS = (torch.bfloat16, torch.float16)
+_SAVE_DTYPE_TARGETS = (torch.bfloat16, torch.float16, MXFP8_E4M3)
 
 
 def _normalize_save_dtype(
@@ -124,14 +125,14 @@ def _normalize_save_dtype(
     rules; a bare dtype means {"**": dtype}. Raises before any I/O."""
     if save_dtype is None:
         return None
-    if isinstance(save_dtype, torch.dtype):
+    if isinstance(save_dtype, torch.dtype) or save_dtype == MXFP8_E4M3:
         rules = [("**", save_dtype)]
     elif isinstance(save_dtype, dict):
         rules = list(save_dtype.items())
     else:
         raise ValueError(
-            "save_dtype must be a torch.dtype or a dict of glob pattern -> "
-            f"torch.dtype, got {type(save_dtype).__name__}"
+            f"save_dtype must be a torch.dtype, {MXFP8_E4M3!r} or a dict of "
+            f"glob pattern -> either, got {save_dtype!r}"
         )
     for pattern, dtype in rules:
         if not isinstance(pattern, str):
@@ -139,7 +140,7 @@ def _normalize_save_dtype(
         if dtype not in _SAVE_DTYPE_TARGETS:
             raise ValueError(
                 f"save_dtype target {dtype!r} (pattern '{pattern}') is not "
-                "supported; allowed: torch.bfloat16, torch.float16"
+                f"supported; allowed: torch.bfloat16, torch.float16, {MXFP8_E4M3!r}"
             )
     return rules
 
@@ -151,17 +152,21 @@ def _resolve_save_dtype(
 ) -> Optional[torch.dtype]:
     """Stored dtype for one leaf, or None to store it unchanged. Only
     strided, non-quantized float32 tensors are narrowed (DTensor and
-    ShardedTensor qualify through their local shards)."""
+    ShardedTensor qualify through their local shards). The block-scaled
+    ``"mxfp8_e4m3"`` takes bfloat16 leaves as well, and plain tensors and
+    Parameters only: a sharded leaf its rule matches is stored as it is."""
     if not rules or not isinstance(obj, torch.Tensor):
         return None
-    if obj.dtype != torch.float32:
+    if obj.dtype not in (torch.float32, torch.bfloat16):
         return None
-    if type(obj) is torch.Tensor or isinstance(obj, torch.nn.Parameter):
-        if obj.is_quantized or obj.layout != torch.strided:
-            return None
+    plain = type(obj) is torch.Tensor or isinstance(obj, torch.nn.Parameter)
+    if plain and (obj.is_quantized or obj.layout != torch.strided):
+        return None
     for pattern, dtype in rules:
         if glob_match(logical_path, pattern):
-            return dtype
+            if dtype == MXFP8_E4M3:
+                return dtype if plain else None
+            return dtype if obj.dtype == torch.float32 else None
     return None
 
 
@@ -1112,6 +1117,10 @@ class Snapshot:
             # a sharded entry may have been recorded without its global shape
             if (plain_entry or entry.shape) and list(shape) != list(entry.shape):
                 sink.note(p, f"shape {tuple(entry.shape)} vs {tuple(shape)}")
+                continue
+            if plain_entry and entry.dtype == MXFP8_E4M3:
+                # lossy by design: the payload is not read at all
+                sink.note(p, f"stored as {MXFP8_E4M3}: not compared")
                 continue
             reqs, _ = prepare_read(entry, obj)
             _compare.attach_compare(reqs, sink, p, entry)
