@@ -10,7 +10,9 @@
   mx          save_dtype="mxfp8_e4m3" — block-scaled fp8, quantised inside
               the gather kernel; 33 bytes stored per 32 elements. With
               --dtype bfloat16 the state is bf16 and only fp32 (here: the
-              plain save) and mx run
+              plain save), mx and mx4 run
+  mx4         save_dtype="mxfp4_e2m1" — block-scaled fp4, the same way;
+              17 bytes stored per 32 elements
 
 Part "save" reports the wall time of Snapshot.take and the stall of
 Snapshot.async_take for each (median of --reps after --warmup, variants
@@ -20,8 +22,10 @@ uncast, direct vs slab mode, in SOURCE bytes per second.
 
 Part "mx_stage" (run with --part mx_stage, not part of "all") reports
 engine.stage + wait of --members tensors of 4096 x 4096 in one launch,
-bf16 and fp32, plain against mxfp8_e4m3: time, stored bytes and the D2H
-rate in stored bytes (profiles/mx_save_measurements.md).
+bf16 and fp32, plain against mxfp8_e4m3 and mxfp4_e2m1: time, stored bytes
+and the D2H rate in stored bytes (profiles/mx_save_measurements.md,
+profiles/mx4_save_measurements.md). With --transposed the members are
+transposed views, which take the kernels' general class.
 
 Each part runs in a fresh child process: the stage part sizes the pinned
 pool's blocks to hold 1 GiB so no run pays a one-off pinned allocation.
@@ -79,9 +83,10 @@ def part_save(args) -> dict:
         },
         "save_dtype": {"save_dtype": torch.bfloat16},
         "mx": {"save_dtype": "mxfp8_e4m3"},
+        "mx4": {"save_dtype": "mxfp4_e2m1"},
     }
     if dtype != torch.float32:
-        variants = {k: variants[k] for k in ("fp32", "mx")}
+        variants = {k: variants[k] for k in ("fp32", "mx", "mx4")}
     take_s = {k: [] for k in variants}
     stall_s = {k: [] for k in variants}
     async_total_s = {k: [] for k in variants}
@@ -139,6 +144,7 @@ def part_stage(args) -> dict:
         "cast_kernel": (halves, [torch.bfloat16, torch.bfloat16]),
         "cast_kernel_single": ([t], [torch.bfloat16]),
         "mx_kernel": (halves, ["mxfp8_e4m3", "mxfp8_e4m3"]),
+        "mx4_kernel": (halves, ["mxfp4_e2m1", "mxfp4_e2m1"]),
     }
     out = {"part": "stage", "source_bytes": GIB, "cases": {}}
     for mode in ("direct", "slab"):
@@ -177,8 +183,14 @@ def part_mx_stage(args) -> dict:
             torch.randn(4096, 4096, device=device).to(dtype)
             for _ in range(args.members)
         ]
+        if args.transposed:
+            tensors = [t.t() for t in tensors]
         src = sum(t.numel() * t.element_size() for t in tensors)
-        for name, outs in (("plain", None), ("mx", ["mxfp8_e4m3"] * len(tensors))):
+        for name, outs in (
+            ("plain", None),
+            ("mx", ["mxfp8_e4m3"] * len(tensors)),
+            ("mx4", ["mxfp4_e2m1"] * len(tensors)),
+        ):
             times = []
             for rep in range(args.warmup + args.reps):
                 torch.cuda.synchronize()
@@ -212,6 +224,7 @@ def main() -> None:
     parser.add_argument("--warmup", type=int, default=2)
     parser.add_argument("--dtype", choices=["float32", "bfloat16"], default="float32")
     parser.add_argument("--members", type=int, default=8)
+    parser.add_argument("--transposed", action="store_true")
     parser.add_argument(
         "--part", choices=["all", "save", "stage", "mx_stage"], default="all"
     )

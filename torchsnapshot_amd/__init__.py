@@ -12,7 +12,7 @@ from .compare import TensorDiff
 from .nonfinite import NonFiniteStateError, find_nonfinite
 from .replication import ReplicatedStateMismatchError, fingerprint_state
 from .rng_state import RNGState
-from .serialization import MXFP8_E4M3
+from .serialization import MXFP4_E2M1, MXFP8_E4M3
 from .snapshot import PendingSnapshot, Snapshot
 from .state_dict import StateDict
 from .stateful import AppState, Stateful
@@ -37,5 +37,6 @@ __all__ = [
     "tensor_histograms",
     "TensorDiff",
     "MXFP8_E4M3",
+    "MXFP4_E2M1",
     "__version__",
 ]

@@ -42,7 +42,7 @@ from .ops.staging import (
     build_pack_items,
     get_staging_engine,
     is_mx,
-    mx_encode,
+    mx_encode_as,
     resolve_lazy,
 )
 from .serialization import SERIALIZER_BUFFER, tensor_as_memoryview
@@ -183,7 +183,7 @@ class BatchedBufferStager(BufferStager):
         for t, off, out_dtype in zip(self.tensors, offsets, self.out_dtypes):
             t = resolve_lazy(t)  # lazy conj/neg views are saved by value
             if is_mx(out_dtype):
-                t = mx_encode(t)  # the payload, as uint8
+                t = mx_encode_as(t, out_dtype)  # the payload, as uint8
             elif out_dtype is not None and out_dtype != t.dtype:
                 t = t.to(out_dtype)
             nbytes = t.numel() * t.element_size()

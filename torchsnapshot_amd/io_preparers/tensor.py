@@ -31,8 +31,8 @@ from ..ops.staging import (
     HIP_EXT_AVAILABLE,
     get_staging_engine,
     is_mx,
-    mx_decode,
-    mx_encode,
+    mx_decode_as,
+    mx_encode_as,
     resolve_lazy,
     scatter_member,
     stored_nbytes,
@@ -104,7 +104,7 @@ class TensorIOPreparer:
     ) -> Tuple[TensorEntry, List[WriteReq]]:
         """``save_dtype`` stores the tensor narrowed to that dtype (the
         entry records the STORED dtype); it requires the plain buffer
-        serializer. Under ``"mxfp8_e4m3"`` the entry also records the
+        serializer. Under a block-scaled format the entry also records the
         tensor's own dtype as ``logical_dtype``."""
         serializer = pick_serializer(tensor)
         if save_dtype == tensor.dtype:
@@ -371,7 +371,7 @@ class TensorBufferStager(BufferStager):
     def _cast_on_host(self, t: torch.Tensor) -> torch.Tensor:
         """``t`` as it is stored under save_dtype, by torch."""
         if is_mx(self.save_dtype):
-            return mx_encode(t)
+            return mx_encode_as(t, self.save_dtype)
         return t.to(self.save_dtype).contiguous()
 
     def _should_copy_cpu_tensor(self, t: torch.Tensor, ctx: StageContext) -> bool:
@@ -426,7 +426,7 @@ class TensorBufferConsumer(PinnedReadConsumer):
         n = 1
         for s in self.entry.shape:
             n *= s
-        flat = mx_decode(u8, n, entry_tensor_dtype(self.entry))
+        flat = mx_decode_as(u8, self.entry.dtype, n, entry_tensor_dtype(self.entry))
         return flat.reshape(tuple(self.entry.shape))
 
     def device_span_target(self):

@@ -49,20 +49,21 @@ class TensorEntry:
     shape: List[int]
     replicated: bool = False
     byte_range: Optional[List[int]] = None
-    # set with dtype "mxfp8_e4m3" (docs/format.md): the dtype of the tensor
-    # that was saved, and of what a read without a target returns
+    # set with a block-scaled dtype, "mxfp8_e4m3" or "mxfp4_e2m1"
+    # (docs/format.md): the dtype of the tensor that was saved, and of what
+    # a read without a target returns
     logical_dtype: Optional[str] = None
 
     KIND = "tensor"
 
     def nbytes_estimate(self) -> int:
-        from .serialization import MXFP8_E4M3, dtype_size_bytes
+        from .serialization import dtype_size_bytes, is_mx, mx_nbytes
 
         n = 1
         for s in self.shape:
             n *= s
-        if self.dtype == MXFP8_E4M3:
-            return 33 * ((n + 31) // 32)
+        if is_mx(self.dtype):
+            return mx_nbytes(n, self.dtype)
         return n * dtype_size_bytes(self.dtype)
 
     def to_dict(self) -> Dict[str, Any]:

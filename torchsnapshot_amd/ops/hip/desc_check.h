@@ -59,6 +59,11 @@ struct Desc {
   // the outer sizes; tensor_base and strides stay in source (f32 or bf16)
   // bytes. vec names the class: 8 = aligned (four lanes per block, 8
   // elements each), 1 = general (one lane per block).
+  // Block-scaled fp4 (mxfp4_e2m1, codes 20..23): the same, with two elements
+  // per flat byte. nbytes = 16 * ceil(n / 32) is the CODES region, the
+  // scales, nbytes / 16 bytes, follow it at flat_off + nbytes, and a 64 KiB
+  // work unit is 4096 blocks. vec 8 = aligned (four lanes per block, 8
+  // elements and 4 code bytes each), 1 = general.
   uint32_t cast;
 };
 
@@ -74,12 +79,25 @@ constexpr uint32_t kCastBF16toMX = 17;  // gather
 constexpr uint32_t kCastMXtoF32 = 18;   // scatter
 constexpr uint32_t kCastMXtoBF16 = 19;  // scatter
 constexpr uint32_t kMxBlock = 32;      // elements per scale byte
+// block-scaled fp4 (mxfp4_e2m1): two elements per code byte
+constexpr uint32_t kCastF32toMX4 = 20;   // gather
+constexpr uint32_t kCastBF16toMX4 = 21;  // gather
+constexpr uint32_t kCastMX4toF32 = 22;   // scatter
+constexpr uint32_t kCastMX4toBF16 = 23;  // scatter
+constexpr uint32_t kMx4BlockBytes = kMxBlock / 2;  // code bytes per block
 
 constexpr bool is_mx_cast(uint32_t code) { return code >= kCastF32toMX; }
+constexpr bool is_mx4_cast(uint32_t code) { return code >= kCastF32toMX4; }
 // tensor-side element size of an mx descriptor
 constexpr uint32_t mx_elem_size(uint32_t code) {
-  return (code == kCastF32toMX || code == kCastMXtoF32) ? 4u : 2u;
+  return (code == kCastF32toMX || code == kCastMXtoF32 ||
+          code == kCastF32toMX4 || code == kCastMX4toF32)
+             ? 4u
+             : 2u;
 }
+// Largest codes region of an mxfp4 descriptor: a code byte is two elements,
+// and the kernels index elements in u32 like everything else
+constexpr uint32_t kMaxMx4CodeBytes = kMaxDescBytes / 2;
 
 // element classes of the non-finite scan (SCAN_* in ops/staging.py)
 constexpr uint32_t kScanF64 = 0;
@@ -161,7 +179,7 @@ inline std::vector<Desc> parse_descs(
       d.sizes[k] = (uint32_t)r[6 + k];
       d.strides[k] = (long long)r[12 + k];
     }
-    if (r[18] > kCastMXtoBF16 ||
+    if (r[18] > kCastMX4toBF16 ||
         (r[18] > kCastF16toF32 && r[18] < kCastF32toMX)) {
       throw std::runtime_error("unknown cast code in descriptor");
     }
@@ -172,10 +190,10 @@ inline std::vector<Desc> parse_descs(
 
 // Which entry point the descriptors are for.
 enum class DescKind {
-  Gather,   // pack_d2h: cast codes 0..2, and 16..17 (mx)
+  Gather,   // pack_d2h: cast codes 0..2, 16..17 (mx) and 20..21 (mx4)
   Scatter,  // scatter_h2d: plain byte scatter, no cast code
-  Unpack,   // unpack_h2d: cast codes 0, 3, 4, and 18..19 (mx); needs a
-            // FlatSide
+  Unpack,   // unpack_h2d: cast codes 0, 3, 4, 18..19 (mx) and 22..23
+            // (mx4); needs a FlatSide
   Scan,     // scan_nonfinite: no cast code; needs one class per descriptor
   Fingerprint,  // fingerprint_tensors: cast codes 0..2; flat_off is a hash
                 // offset and must be a multiple of vec
@@ -239,7 +257,8 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
     switch (kind) {
       case DescKind::Gather:
         if (d.cast == kCastBF16toF32 || d.cast == kCastF16toF32 ||
-            d.cast > kCastBF16toMX) {
+            d.cast == kCastMXtoF32 || d.cast == kCastMXtoBF16 ||
+            d.cast > kCastBF16toMX4) {
           refuse("widening cast descriptors are scatter-only (unpack_h2d)");
         }
         break;
@@ -249,7 +268,8 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
         break;
       case DescKind::Unpack:
         if ((cast && d.cast <= kCastF16) || d.cast == kCastF32toMX ||
-            d.cast == kCastBF16toMX) {
+            d.cast == kCastBF16toMX || d.cast == kCastF32toMX4 ||
+            d.cast == kCastBF16toMX4) {
           refuse("does not support narrowing cast descriptors");
         }
         break;
@@ -284,38 +304,48 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
     }
     const uint32_t v = d.vec;
     if (is_mx_cast(d.cast)) {
-      // Block-scaled fp8: only Gather and Unpack let these codes through.
-      // The rules are the accesses mx_gather_* and mx_scatter_* make.
-      if (d.nbytes % kMxBlock != 0) refuse("mx: nbytes must be whole blocks");
-      if (v != 8 && v != 1) refuse("mx: vec must be 8 (aligned) or 1 (general)");
-      if (d.row_bytes == 0) refuse("mx: empty row");
+      // Block-scaled fp8 and fp4: only Gather and Unpack let these codes
+      // through. The rules are the accesses mx_gather_* and mx_scatter_*
+      // (mx4_* for fp4) make; fp4 differs in the code bytes per block and
+      // in its size cap.
+      const bool fp4 = is_mx4_cast(d.cast);
+      const uint32_t bb = fp4 ? kMx4BlockBytes : kMxBlock;
+      auto refuse_mx = [&](const char* what) {
+        refuse(((fp4 ? "mx4: " : "mx: ") + std::string(what)).c_str());
+      };
+      if (d.nbytes % bb != 0) refuse_mx("nbytes must be whole blocks");
+      if (fp4 && d.nbytes > kMaxMx4CodeBytes) {
+        refuse_mx("too many elements (> 2^32 - 64 Ki)");
+      }
+      if (v != 8 && v != 1) refuse_mx("vec must be 8 (aligned) or 1 (general)");
+      if (d.row_bytes == 0) refuse_mx("empty row");
       unsigned long long n = d.row_bytes;
       for (uint32_t k = 0; k < d.ndim; ++k) n *= d.sizes[k];
-      if ((n + kMxBlock - 1) / kMxBlock * kMxBlock != d.nbytes) {
-        refuse("mx: nbytes is not the block-padded element count");
+      if ((n + kMxBlock - 1) / kMxBlock * bb != d.nbytes) {
+        refuse_mx("nbytes is not the block-padded element count");
       }
-      // codes go as 8 B and 16 B accesses, scales as 16 B ones
-      if (d.flat_off % 16 != 0) refuse("mx: flat offset must be 16-aligned");
+      // codes go as 8 B (fp4: 4 B) and 16 B accesses, scales as 16 B ones
+      if (d.flat_off % 16 != 0) refuse_mx("flat offset must be 16-aligned");
       if (flat != nullptr) {
         const uintptr_t base =
             flat->slab_ptr != 0 ? flat->slab_ptr : flat->pinned_ptr;
-        if (base % 16 != 0) refuse("mx: flat side must be 16-aligned");
+        if (base % 16 != 0) refuse_mx("flat side must be 16-aligned");
         const unsigned long long stored =
-            (unsigned long long)d.nbytes + d.nbytes / kMxBlock;
+            (unsigned long long)d.nbytes + d.nbytes / bb;
         if (d.flat_off > flat->total_bytes ||
             stored > flat->total_bytes - d.flat_off) {
-          refuse("mx: scales region outside the slab");
+          refuse_mx("scales region outside the slab");
         }
       }
       if (v == 8 && d.ndim != 0 && d.row_bytes % kMxBlock != 0) {
-        refuse("mx: aligned class needs rows of 32k elements");
+        refuse_mx("aligned class needs rows of 32k elements");
       }
       const unsigned long long align = v == 8 ? 16 : mx_elem_size(d.cast);
       bool ok = reinterpret_cast<uintptr_t>(d.tensor_base) % align == 0;
       for (uint32_t k = 0; k < d.ndim; ++k) {
         ok = ok && (unsigned long long)d.strides[k] % align == 0;
       }
-      if (!ok) refuse("mx: tensor side not aligned for its class");
+      if (!ok) refuse_mx("tensor side not aligned for its class");
       continue;
     }
     if (v != 16 && v != 8 && v != 4 && v != 2 && (v != 1 || cast)) {

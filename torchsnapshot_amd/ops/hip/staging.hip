@@ -678,7 +678,8 @@ __global__ __launch_bounds__(kBlockThreads) void unpack_kernel(
 //     in 2 KiB of LDS and, after a workgroup barrier, written as 16 B
 //     pieces; only the payload's last, short piece goes narrower. The
 //     scatter mirrors this: it first loads the unit's scales into LDS with
-//     16 B loads (the flat side is read exactly once), then decodes
+//     16 B loads (the flat side is read exactly once), then decodes. The
+//     buffer is sized for fp4's units below, 4096 blocks and 4 KiB
 //   - conversion is integer arithmetic on the bit patterns, like the casts
 //     above: f32 subnormals, e4m3 subnormals and ties come out the same in
 //     every wave mode. A bf16 source is its f32 pattern (<< 16)
@@ -972,6 +973,210 @@ __device__ unsigned long long mx_gather_unit(const Desc& d, char* flat_base,
                                         (e - s) >> 5, scales_off);
 }
 
+// ---------------------------------------------------------------------------
+// block-scaled fp4 (mxfp4_e2m1; docs/format.md): the same payload with two
+// e2m1 codes per byte, [codes: 16*nb bytes][scales: nb bytes]; element 2j of
+// a block is the low nibble of its byte j. The descriptor's flat range is
+// again the codes region, so a 64 KiB work unit is 4096 blocks (131072
+// elements) and owns 4096 scale bytes at flat_off + nbytes + s / 16.
+//
+//   - aligned class: four lanes per block as above, 8 elements each; a lane
+//     packs its eight nibbles into one dword, 256 contiguous bytes per wave
+//   - general class: one lane per block, two passes over its elements: the
+//     first takes amax, the second reads them again (from cache) and encodes
+//     eight at a time into one dword. Nothing is indexed at run time, so the
+//     block never sits in private memory; the 16 code bytes leave as one
+//     16 B store
+//   - e2m1 has no NaN and no Inf: a block with a non-finite element stores
+//     X = 0xFF (the whole block decodes to NaN), its non-finite elements
+//     magnitude 7. Whether a block has one is a ballot over its four lanes
+//   - scales, psum64 and mixing with other descriptors: as for fp8
+// ---------------------------------------------------------------------------
+
+constexpr uint32_t kMx4UnitBlocks = kWorkUnitBytes / kMx4BlockBytes;  // 4096
+
+// E of a block from the pattern of its amax (finite, sign cleared):
+// floor(log2 amax) - 2, one more when amax * 2^-E would exceed 6 = 1.5 * 2^2,
+// at least -127. Zero and f32 subnormals end at -127.
+__device__ __host__ inline int mx4_block_exp(uint32_t amax) {
+  if (amax < 0x00800000u) return -127;
+  const int e = (int)(amax >> 23) - 129 + ((amax & 0x007FFFFFu) > 0x00400000u);
+  return e < -127 ? -127 : e;
+}
+
+// e2m1 code (4 bits) of the f32 pattern u scaled by 2^-E, round to nearest
+// even on the grid 0, 0.5, 1, 1.5, 2, 3, 4, 6, clamped to +-6; NaN and +-Inf
+// become magnitude 7 with the sign kept.
+__device__ __host__ inline uint32_t mx4_code(uint32_t u, int E) {
+  const uint32_t sign = (u >> 28) & 0x8u;
+  const uint32_t a = u & 0x7FFFFFFFu;
+  if (a >= 0x7F800000u) return sign | 0x7u;
+  if (a == 0u) return sign;
+  // |x| = M * 2^(ex - 23) with M in [2^23, 2^24)
+  uint32_t M = a & 0x007FFFFFu;
+  int ex = (int)(a >> 23) - 127;
+  if (a < 0x00800000u) {
+    const int lz = __builtin_clz(M) - 8;  // 1..23
+    M <<= lz;
+    ex = -126 - lz;
+  } else {
+    M |= 0x00800000u;
+  }
+  // y = |x| * 2^-E has exponent t. From t = 0 up it is an e2m1 normal with
+  // step 2^(t-1): q = RNE(M / 2^22) in [2, 4], and a carry to 4 runs into
+  // the exponent field. Below, the step stays 2^-1 (the one e2m1 subnormal).
+  const int t = ex - E;
+  const int shift = 22 + (t < 0 ? -t : 0);
+  const uint32_t sh = shift > 26 ? 26u : (uint32_t)shift;  // >= 25 gives 0
+  const uint32_t q = (M + ((1u << (sh - 1)) - 1u) + ((M >> sh) & 1u)) >> sh;
+  const uint32_t code = t >= 0 ? ((uint32_t)t << 1) + q : q;
+  return sign | (code > 0x7u ? 0x7u : code);
+}
+
+// f32 pattern of e2m1(code) * 2^(X - 127): exact, f32 subnormals included
+__device__ __host__ inline uint32_t mx4_decode_bits(uint32_t c, uint32_t X) {
+  const uint32_t sign = (c & 0x8u) << 28;
+  const uint32_t m = c & 0x7u;
+  if (X == 0xFFu) return sign | 0x7FC00000u;
+  if (m == 0u) return sign;
+  // 0.5 is the subnormal; from 1 on, 2^(ef-1) * (1 + mant / 2)
+  const int ex = m == 1u ? -1 : (int)(m >> 1) - 1;
+  const uint32_t frac = m == 1u ? 0u : (m & 1u) << 22;
+  const int biased = ex + (int)X;  // ex + (X - 127) + 127
+  if (biased >= 255) return sign | 0x7F800000u;
+  if (biased > 0) return sign | ((uint32_t)biased << 23) | frac;
+  // only the top two bits of the significand are set and the shift is at
+  // most 2: nothing is lost
+  return sign | ((0x00800000u | frac) >> (1 - biased));
+}
+
+// Aligned gather of [s, e) of the codes region of one work unit, 4 code bytes
+// per lane; the unit's scale bytes go to `lds`.
+template <bool BF16, bool HASH>
+__device__ unsigned long long mx4_gather_aligned(const Desc& d, char* flat_base,
+                                                 uint32_t s, uint32_t e,
+                                                 unsigned char* lds) {
+  char* flat = flat_base + d.flat_off;
+  unsigned long long h = 0;
+  for (uint32_t i = s + threadIdx.x * 4; i < e; i += kBlockThreads * 4) {
+    uint32_t valid;
+    const char* src = mx_aligned_addr<BF16 ? 2 : 4>(d, 2 * i, valid);
+    uint32_t v[8];
+    mx_load8<BF16>(src, valid, v);
+    uint32_t amax = 0;
+    bool nonfinite = false;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      amax = max(amax, mx_amax_of(v[k]));
+      nonfinite = nonfinite || (v[k] & 0x7FFFFFFFu) >= 0x7F800000u;
+    }
+    // e and the unit are whole blocks: the four lanes of a block are all
+    // here or all gone
+    amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
+    amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2, 64));
+    const bool block_nonfinite =
+        ((__ballot(nonfinite) >> (threadIdx.x & 60u)) & 0xFull) != 0;
+    const int E = mx4_block_exp(amax);
+    uint32_t o = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o |= mx4_code(v[k], E) << (4 * k);
+    *reinterpret_cast<uint32_t*>(flat + i) = o;
+    if (HASH) h += psum_piece(o, d.flat_off + i);
+    if ((threadIdx.x & 3u) == 0u) {
+      lds[(i - s) >> 4] = block_nonfinite ? 0xFFu : (unsigned char)(E + 127);
+    }
+  }
+  return h;
+}
+
+// The general class's walk: the f32 pattern of the element at (p, col), then
+// one step on in row-major order; `more` is false at the tensor's last element
+template <bool BF16>
+__device__ __forceinline__ uint32_t mx_walk_load(const Desc& d, const char*& p,
+                                                 uint32_t& row, uint32_t& col,
+                                                 bool more) {
+  const char* q = p + (unsigned long long)(BF16 ? 2 : 4) * col;
+  const uint32_t u = BF16 ? (uint32_t)*reinterpret_cast<const uint16_t*>(q) << 16
+                          : *reinterpret_cast<const uint32_t*>(q);
+  if (++col == d.row_bytes && more) {
+    col = 0;
+    p = d.tensor_base + row_offset(d, ++row);
+  }
+  return u;
+}
+
+// General gather: one lane per block, walking rows twice.
+template <bool BF16, bool HASH>
+__device__ unsigned long long mx4_gather_general(const Desc& d, char* flat_base,
+                                                 uint32_t s, uint32_t e,
+                                                 unsigned char* lds) {
+  char* flat = flat_base + d.flat_off;
+  const uint32_t n = mx_numel(d);
+  unsigned long long h = 0;
+  for (uint32_t i0 = s + threadIdx.x * kMx4BlockBytes; i0 < e;
+       i0 += kBlockThreads * kMx4BlockBytes) {
+    // the block's first element exists: nbytes is ceil(n / 32) blocks
+    const uint32_t el0 = 2 * i0;
+    const uint32_t count = min(n - el0, kMxBlock);
+    const uint32_t row0 = el0 / d.row_bytes;
+    const uint32_t col0 = el0 - row0 * d.row_bytes;
+    const char* const p0 = d.tensor_base + row_offset(d, row0);
+
+    uint32_t row = row0, col = col0;
+    const char* p = p0;
+    uint32_t amax = 0;
+    bool nonfinite = false;
+    for (uint32_t j = 0; j < count; ++j) {
+      const uint32_t u = mx_walk_load<BF16>(d, p, row, col, j + 1 < count);
+      amax = max(amax, mx_amax_of(u));
+      nonfinite = nonfinite || (u & 0x7FFFFFFFu) >= 0x7F800000u;
+    }
+    const int E = mx4_block_exp(amax);
+
+    row = row0, col = col0, p = p0;
+    uint4 o = make_uint4(0u, 0u, 0u, 0u);
+    for (uint32_t j0 = 0; j0 < count; j0 += 8) {
+      uint32_t w = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < 8; ++k) {
+        if (j0 + k < count) {
+          const uint32_t u =
+              mx_walk_load<BF16>(d, p, row, col, j0 + k + 1 < count);
+          w |= mx4_code(u, E) << (4 * k);
+        }
+      }
+      // selects, not an index: `o` stays in registers
+      if (j0 == 0) o.x = w;
+      else if (j0 == 8) o.y = w;
+      else if (j0 == 16) o.z = w;
+      else o.w = w;
+    }
+    *reinterpret_cast<uint4*>(flat + i0) = o;
+    if (HASH) h += psum_regs<16>(o, d.flat_off + i0);
+    lds[(i0 - s) >> 4] = nonfinite ? 0xFFu : (unsigned char)(E + 127);
+  }
+  return h;
+}
+
+// One mxfp4 descriptor's work unit of the gather: codes, then the scales.
+template <bool HASH>
+__device__ unsigned long long mx4_gather_unit(const Desc& d, char* flat_base,
+                                              uint32_t s, uint32_t e,
+                                              unsigned char* lds) {
+  const bool bf16 = d.cast == kCastBF16toMX4;
+  unsigned long long h;
+  if (d.vec == 8) {
+    h = bf16 ? mx4_gather_aligned<true, HASH>(d, flat_base, s, e, lds)
+             : mx4_gather_aligned<false, HASH>(d, flat_base, s, e, lds);
+  } else {
+    h = bf16 ? mx4_gather_general<true, HASH>(d, flat_base, s, e, lds)
+             : mx4_gather_general<false, HASH>(d, flat_base, s, e, lds);
+  }
+  const unsigned long long scales_off = d.flat_off + d.nbytes + (s >> 4);
+  return h + mx_move_scales<true, HASH>(flat_base + scales_off, lds,
+                                        (e - s) >> 4, scales_off);
+}
+
 // pack_kernel for batches that hold an mx descriptor; plain and cast
 // descriptors of the same slab take pack_kernel's own routes.
 template <bool HASH>
@@ -980,13 +1185,15 @@ __global__ __launch_bounds__(kBlockThreads) void pack_mx_kernel(
     const unsigned long long* __restrict__ wu_prefix,
     unsigned long long total_wus, char* __restrict__ flat_base,
     unsigned long long* __restrict__ hash_out) {
-  __shared__ uint4 lds_scales[kMxUnitBlocks / 16];
+  __shared__ uint4 lds_scales[kMx4UnitBlocks / 16];
   unsigned char* lds = reinterpret_cast<unsigned char*>(lds_scales);
   for_each_work_unit(
       descs, n, wu_prefix, total_wus,
       [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
         unsigned long long h = 0;
-        if (is_mx_cast(d.cast)) {
+        if (is_mx4_cast(d.cast)) {
+          h = mx4_gather_unit<HASH>(d, flat_base, s, e, lds);
+        } else if (is_mx_cast(d.cast)) {
           h = mx_gather_unit<HASH>(d, flat_base, s, e, lds);
         } else if (d.cast != kCastNone) {
           switch (d.vec) {
@@ -1016,6 +1223,31 @@ __device__ __forceinline__ uint32_t mx_out(uint32_t code, uint32_t X) {
   return BF16 ? (f32_to_bf16_bits(f) & 0xFFFFu) : f;
 }
 
+// 8 consecutive decoded elements, as mx_out gives them, to an aligned-class
+// target: 16 B stores; the ones from `valid` on do not exist
+template <bool BF16>
+__device__ __forceinline__ void mx_store8(char* dst, uint32_t valid,
+                                          const uint32_t (&o)[8]) {
+  if (valid >= 8) {
+    if (BF16) {
+      *reinterpret_cast<uint4*>(dst) =
+          make_uint4(o[0] | (o[1] << 16), o[2] | (o[3] << 16),
+                     o[4] | (o[5] << 16), o[6] | (o[7] << 16));
+    } else {
+      *reinterpret_cast<uint4*>(dst) = make_uint4(o[0], o[1], o[2], o[3]);
+      *reinterpret_cast<uint4*>(dst + 16) = make_uint4(o[4], o[5], o[6], o[7]);
+    }
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) {
+      if (k < valid) {
+        if (BF16) reinterpret_cast<uint16_t*>(dst)[k] = (uint16_t)o[k];
+        else reinterpret_cast<uint32_t*>(dst)[k] = o[k];
+      }
+    }
+  }
+}
+
 // Aligned scatter of [s, e) of the codes region; the unit's scales are in
 // `lds` already.
 template <bool BF16, bool HASH>
@@ -1040,24 +1272,7 @@ __device__ unsigned long long mx_scatter_aligned(const Desc& d,
     for (int k = 0; k < 8; ++k) {
       o[k] = mx_out<BF16>(((k < 4 ? c.x : c.y) >> (8 * (k & 3))) & 0xFFu, X);
     }
-    if (valid >= 8) {
-      if (BF16) {
-        *reinterpret_cast<uint4*>(dst) =
-            make_uint4(o[0] | (o[1] << 16), o[2] | (o[3] << 16),
-                       o[4] | (o[5] << 16), o[6] | (o[7] << 16));
-      } else {
-        *reinterpret_cast<uint4*>(dst) = make_uint4(o[0], o[1], o[2], o[3]);
-        *reinterpret_cast<uint4*>(dst + 16) = make_uint4(o[4], o[5], o[6], o[7]);
-      }
-    } else {
-#pragma unroll
-      for (uint32_t k = 0; k < 8; ++k) {
-        if (k < valid) {
-          if (BF16) reinterpret_cast<uint16_t*>(dst)[k] = (uint16_t)o[k];
-          else reinterpret_cast<uint32_t*>(dst)[k] = o[k];
-        }
-      }
-    }
+    mx_store8<BF16>(dst, valid, o);
   }
   return h;
 }
@@ -1127,6 +1342,101 @@ __device__ unsigned long long mx_scatter_unit(const Desc& d,
   return h;
 }
 
+// the decoded fp4 element as the target stores it; exact in bf16 as well, a
+// decoded value has at most two significant bits
+template <bool BF16>
+__device__ __forceinline__ uint32_t mx4_out(uint32_t code, uint32_t X) {
+  const uint32_t f = mx4_decode_bits(code, X);
+  return BF16 ? (f32_to_bf16_bits(f) & 0xFFFFu) : f;
+}
+
+// Aligned fp4 scatter of [s, e) of the codes region: 4 code bytes in, 8
+// elements out per lane; the unit's scales are in `lds` already.
+template <bool BF16, bool HASH>
+__device__ unsigned long long mx4_scatter_aligned(const Desc& d,
+                                                  const char* flat_base,
+                                                  uint32_t s, uint32_t e,
+                                                  unsigned long long hash_off,
+                                                  const unsigned char* lds) {
+  const char* flat = flat_base + d.flat_off;
+  unsigned long long h = 0;
+  for (uint32_t i = s + threadIdx.x * 4; i < e; i += kBlockThreads * 4) {
+    const uint32_t c = *reinterpret_cast<const uint32_t*>(flat + i);
+    if (HASH) h += psum_piece(c, hash_off + i);
+    const uint32_t X = lds[(i - s) >> 4];
+    uint32_t valid;
+    char* dst =
+        const_cast<char*>(mx_aligned_addr<BF16 ? 2 : 4>(d, 2 * i, valid));
+    uint32_t o[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = mx4_out<BF16>((c >> (4 * k)) & 0xFu, X);
+    mx_store8<BF16>(dst, valid, o);
+  }
+  return h;
+}
+
+// General fp4 scatter: one lane per block, walking rows.
+template <bool BF16, bool HASH>
+__device__ unsigned long long mx4_scatter_general(const Desc& d,
+                                                  const char* flat_base,
+                                                  uint32_t s, uint32_t e,
+                                                  unsigned long long hash_off,
+                                                  const unsigned char* lds) {
+  constexpr int TS = BF16 ? 2 : 4;
+  const char* flat = flat_base + d.flat_off;
+  char* base = const_cast<char*>(d.tensor_base);
+  const uint32_t rb = d.row_bytes;
+  const uint32_t n = mx_numel(d);
+  unsigned long long h = 0;
+  for (uint32_t i0 = s + threadIdx.x * kMx4BlockBytes; i0 < e;
+       i0 += kBlockThreads * kMx4BlockBytes) {
+    const uint4 c = *reinterpret_cast<const uint4*>(flat + i0);
+    if (HASH) h += psum_regs<16>(c, hash_off + i0);
+    const uint32_t X = lds[(i0 - s) >> 4];
+    const uint32_t el0 = 2 * i0;
+    const uint32_t count = min(n - el0, kMxBlock);
+    uint32_t row = el0 / rb;
+    uint32_t col = el0 - row * rb;
+    char* p = base + row_offset(d, row);
+    for (uint32_t j = 0; j < count; ++j) {
+      // selects, not an index: `c` stays in registers
+      const uint32_t w = j < 8 ? c.x : j < 16 ? c.y : j < 24 ? c.z : c.w;
+      const uint32_t o = mx4_out<BF16>((w >> (4 * (j & 7u))) & 0xFu, X);
+      char* q = p + (unsigned long long)TS * col;
+      if (BF16) *reinterpret_cast<uint16_t*>(q) = (uint16_t)o;
+      else *reinterpret_cast<uint32_t*>(q) = o;
+      if (++col == rb && j + 1 < count) {
+        col = 0;
+        p = base + row_offset(d, ++row);
+      }
+    }
+  }
+  return h;
+}
+
+// One mxfp4 descriptor's work unit of the scatter: the scales, then the codes.
+template <bool HASH>
+__device__ unsigned long long mx4_scatter_unit(const Desc& d,
+                                               const char* flat_base,
+                                               uint32_t s, uint32_t e,
+                                               unsigned long long hash_off,
+                                               unsigned char* lds) {
+  const unsigned long long scales_off =
+      (unsigned long long)d.nbytes + (s >> 4);
+  unsigned long long h = mx_move_scales<false, HASH>(
+      const_cast<char*>(flat_base) + d.flat_off + scales_off, lds, (e - s) >> 4,
+      hash_off + scales_off);
+  const bool bf16 = d.cast == kCastMX4toBF16;
+  if (d.vec == 8) {
+    h += bf16 ? mx4_scatter_aligned<true, HASH>(d, flat_base, s, e, hash_off, lds)
+              : mx4_scatter_aligned<false, HASH>(d, flat_base, s, e, hash_off, lds);
+  } else {
+    h += bf16 ? mx4_scatter_general<true, HASH>(d, flat_base, s, e, hash_off, lds)
+              : mx4_scatter_general<false, HASH>(d, flat_base, s, e, hash_off, lds);
+  }
+  return h;
+}
+
 // unpack_kernel for batches that hold an mx descriptor
 template <bool HASH>
 __global__ __launch_bounds__(kBlockThreads) void unpack_mx_kernel(
@@ -1135,7 +1445,7 @@ __global__ __launch_bounds__(kBlockThreads) void unpack_mx_kernel(
     unsigned long long total_wus, const char* __restrict__ flat_base,
     unsigned long long* __restrict__ hash_out,
     unsigned long long hash_byte0) {
-  __shared__ uint4 lds_scales[kMxUnitBlocks / 16];
+  __shared__ uint4 lds_scales[kMx4UnitBlocks / 16];
   unsigned char* lds = reinterpret_cast<unsigned char*>(lds_scales);
   for_each_work_unit(
       descs, n, wu_prefix, total_wus,
@@ -1143,7 +1453,9 @@ __global__ __launch_bounds__(kBlockThreads) void unpack_mx_kernel(
         const unsigned long long ho = hash_byte0 + d.flat_off;
         const char* fb = flat_base;
         unsigned long long h = 0;
-        if (is_mx_cast(d.cast)) {
+        if (is_mx4_cast(d.cast)) {
+          h = mx4_scatter_unit<HASH>(d, fb, s, e, ho, lds);
+        } else if (is_mx_cast(d.cast)) {
           h = mx_scatter_unit<HASH>(d, fb, s, e, ho, lds);
         } else if (d.cast != kCastNone) {
           switch (d.vec) {

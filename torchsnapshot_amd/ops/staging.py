@@ -33,7 +33,7 @@ from typing import Any, Callable, Dict, Iterator, List, Optional, Sequence, Tupl
 import torch
 
 from .. import knobs
-from ..serialization import MXFP8_E4M3
+from ..serialization import MXFP4_E2M1, MXFP8_E4M3, is_mx, mx_nbytes
 
 ALIGN = 256  # slab alignment per packed tensor
 
@@ -133,6 +133,8 @@ class PackItem:
     def stored_bytes(self) -> int:
         """Payload bytes in the slab: ``nbytes``, and for a block-scaled
         item the scale bytes that follow the codes region."""
+        if self.cast >= CAST_F32_TO_MX4:
+            return self.nbytes + self.nbytes // (MX_BLOCK // 2)
         if self.cast >= CAST_F32_TO_MX:
             return self.nbytes + self.nbytes // MX_BLOCK
         return self.nbytes
@@ -142,31 +144,32 @@ CAST_NONE = 0
 CAST_F32_TO_BF16 = 1
 CAST_F32_TO_F16 = 2
 
-# Block-scaled fp8 (docs/format.md). It is no torch dtype: wherever a stored
-# dtype is named, this string stands for it.
+# Block-scaled fp8 and fp4 (docs/format.md). They are no torch dtypes:
+# wherever a stored dtype is named, their strings stand for them
+# (serialization.is_mx).
 MX_BLOCK = 32
 CAST_F32_TO_MX = 16
 CAST_BF16_TO_MX = 17
+CAST_F32_TO_MX4 = 20
+CAST_BF16_TO_MX4 = 21
 
-StoredDtype = Any  # a torch.dtype, or MXFP8_E4M3
+StoredDtype = Any  # a torch.dtype, MXFP8_E4M3 or MXFP4_E2M1
 
 _CAST_CODES = {
     (torch.float32, torch.bfloat16): CAST_F32_TO_BF16,
     (torch.float32, torch.float16): CAST_F32_TO_F16,
     (torch.float32, MXFP8_E4M3): CAST_F32_TO_MX,
     (torch.bfloat16, MXFP8_E4M3): CAST_BF16_TO_MX,
+    (torch.float32, MXFP4_E2M1): CAST_F32_TO_MX4,
+    (torch.bfloat16, MXFP4_E2M1): CAST_BF16_TO_MX4,
 }
 
 
-def is_mx(dtype: Any) -> bool:
-    return isinstance(dtype, str) and dtype == MXFP8_E4M3
-
-
 def stored_nbytes(numel: int, dtype: StoredDtype) -> int:
-    """Payload bytes of ``numel`` elements stored as ``dtype``: 33 bytes per
-    block of 32 for block-scaled fp8."""
+    """Payload bytes of ``numel`` elements stored as ``dtype``: per block of
+    32, 33 bytes for block-scaled fp8 and 17 for fp4."""
     if is_mx(dtype):
-        return 33 * ((numel + MX_BLOCK - 1) // MX_BLOCK)
+        return mx_nbytes(numel, dtype)
     return numel * dtype.itemsize
 
 
@@ -180,7 +183,7 @@ def cast_code(src: torch.dtype, dst: Optional[StoredDtype]) -> int:
         raise ValueError(
             f"the gather kernel cannot cast {src} to {dst}; supported: "
             "float32 -> bfloat16, float32 -> float16, float32 or bfloat16 "
-            f"-> {MXFP8_E4M3!r}"
+            f"-> {MXFP8_E4M3!r} or {MXFP4_E2M1!r}"
         )
     return code
 
@@ -191,17 +194,22 @@ def _pow2(k: torch.Tensor) -> torch.Tensor:
     return ((k + 1023) << 52).view(torch.float64)
 
 
+def _mx_blocks(t: torch.Tensor) -> torch.Tensor:
+    """``t``'s row-major elements in float64 as (blocks, 32), the last block
+    padded with zeros."""
+    x = resolve_lazy(t.detach()).reshape(-1).to(torch.float64)
+    nb = (x.numel() + MX_BLOCK - 1) // MX_BLOCK
+    if x.numel() != nb * MX_BLOCK:
+        x = torch.cat([x, x.new_zeros(nb * MX_BLOCK - x.numel())])
+    return x.reshape(nb, MX_BLOCK)
+
+
 def mx_encode(t: torch.Tensor) -> torch.Tensor:
     """The mxfp8_e4m3 payload of ``t`` (float32 or bfloat16, any layout) as
     a uint8 tensor on ``t``'s device: 32 code bytes per block of its
     row-major elements, then one scale byte per block (docs/format.md). The
     torch expression of what the gather kernel stores, byte for byte."""
-    x = resolve_lazy(t.detach()).reshape(-1).to(torch.float64)
-    n = x.numel()
-    nb = (n + MX_BLOCK - 1) // MX_BLOCK
-    if n != nb * MX_BLOCK:
-        x = torch.cat([x, x.new_zeros(nb * MX_BLOCK - n)])
-    x = x.reshape(nb, MX_BLOCK)
+    x = _mx_blocks(t)
     finite = torch.isfinite(x)
     amax = torch.where(finite, x.abs(), 0.0).amax(dim=1)
     # amax = m * 2^e with m in [0.5, 1): floor(log2 amax) is e - 1
@@ -234,6 +242,71 @@ def mx_decode(payload: torch.Tensor, n: int, dtype: torch.dtype) -> torch.Tensor
     return x.reshape(-1)[:n].to(torch.float32).to(dtype)
 
 
+def mx4_encode(t: torch.Tensor) -> torch.Tensor:
+    """The mxfp4_e2m1 payload of ``t`` (float32 or bfloat16, any layout) as
+    a uint8 tensor on ``t``'s device: 16 code bytes per block of its
+    row-major elements, the even element in the low nibble, then one scale
+    byte per block (docs/format.md). The torch expression of what the gather
+    kernel stores, byte for byte."""
+    x = _mx_blocks(t)
+    finite = torch.isfinite(x)
+    amax = torch.where(finite, x.abs(), 0.0).amax(dim=1)
+    # amax = m * 2^e with m in [0.5, 1): floor(log2 amax) is e - 1
+    exp = torch.frexp(amax).exponent.to(torch.int64) - 3
+    exp = exp + (amax * _pow2(-exp) > 6.0).to(torch.int64)
+    exp = torch.where(amax == 0, -127, exp).clamp_(min=-127)
+    y = torch.where(finite, x, 0.0).abs() * _pow2(-exp)[:, None]
+    # the code is the number of grid midpoints at or below y; a midpoint
+    # itself goes to the even code, so every other comparison is strict
+    mag = sum(
+        (y >= mid) if k % 2 else (y > mid)
+        for k, mid in enumerate((0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0))
+    )
+    mag = torch.where(finite, mag, 7).to(torch.uint8)
+    codes = mag + torch.signbit(x).to(torch.uint8) * 8
+    packed = codes[:, 0::2] | (codes[:, 1::2] << 4)
+    scales = torch.where(finite.all(dim=1), exp + 127, 255).to(torch.uint8)
+    return torch.cat([packed.reshape(-1), scales])
+
+
+_E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def mx4_decode(payload: torch.Tensor, n: int, dtype: torch.dtype) -> torch.Tensor:
+    """The ``n`` elements of an mxfp4_e2m1 ``payload`` (uint8, 17 bytes per
+    block) as a 1-D ``dtype`` tensor on its device: grid value times
+    2^(X - 127), exact in float32 and in bfloat16; a scale byte of 0xFF gives
+    NaN. The torch expression of what the scatter kernel restores."""
+    nb = (n + MX_BLOCK - 1) // MX_BLOCK
+    if payload.numel() != 17 * nb:
+        raise ValueError(
+            f"mxfp4_e2m1 payload of {n} elements must be {17 * nb} bytes, "
+            f"got {payload.numel()}"
+        )
+    packed = payload[: 16 * nb]
+    codes = torch.stack([packed & 0xF, packed >> 4], dim=1).reshape(nb, MX_BLOCK)
+    grid = torch.tensor(_E2M1_GRID, dtype=torch.float64, device=payload.device)
+    values = grid[(codes & 7).long()] * (1.0 - 2.0 * (codes >> 3).double())
+    scale = payload[16 * nb :].to(torch.int64) - 127
+    x = values * _pow2(scale)[:, None]
+    x = torch.where((scale == 128)[:, None], float("nan"), x)
+    return x.reshape(-1)[:n].to(torch.float32).to(dtype)
+
+
+def mx_encode_as(t: torch.Tensor, stored: str) -> torch.Tensor:
+    """``t``'s payload in the block-scaled format ``stored``."""
+    return mx4_encode(t) if stored == MXFP4_E2M1 else mx_encode(t)
+
+
+def mx_decode_as(
+    payload: torch.Tensor, stored: str, n: int, dtype: torch.dtype
+) -> torch.Tensor:
+    """The ``n`` elements of a ``payload`` in the block-scaled format
+    ``stored`` as a 1-D ``dtype`` tensor."""
+    decode = mx4_decode if stored == MXFP4_E2M1 else mx_decode
+    return decode(payload, n, dtype)
+
+
 # widening on restore (scatter only): the descriptor convention is the cast
 # one, flat side in stored 2-byte units and tensor side in float32 bytes
 CAST_BF16_TO_F32 = 3
@@ -242,12 +315,16 @@ CAST_F16_TO_F32 = 4
 # bytes
 CAST_MX_TO_F32 = 18
 CAST_MX_TO_BF16 = 19
+CAST_MX4_TO_F32 = 22
+CAST_MX4_TO_BF16 = 23
 
 _WIDEN_CODES = {
     (torch.bfloat16, torch.float32): CAST_BF16_TO_F32,
     (torch.float16, torch.float32): CAST_F16_TO_F32,
     (MXFP8_E4M3, torch.float32): CAST_MX_TO_F32,
     (MXFP8_E4M3, torch.bfloat16): CAST_MX_TO_BF16,
+    (MXFP4_E2M1, torch.float32): CAST_MX4_TO_F32,
+    (MXFP4_E2M1, torch.bfloat16): CAST_MX4_TO_BF16,
 }
 
 
@@ -261,7 +338,7 @@ def widen_code(stored: StoredDtype, target: torch.dtype) -> int:
         raise ValueError(
             f"the scatter kernel cannot restore {stored} into {target}; "
             "supported: equal dtypes, bfloat16 -> float32, float16 -> float32, "
-            f"{MXFP8_E4M3!r} -> float32 or bfloat16"
+            f"{MXFP8_E4M3!r} or {MXFP4_E2M1!r} -> float32 or bfloat16"
         )
     return code
 
@@ -382,7 +459,7 @@ def _build_cast_item(
     if t.numel() == 0:
         return PackItem(t.data_ptr(), off, 0, 0, [], [], 1, CAST_NONE)
     if is_mx(out_dtype):
-        return _build_mx_item(t, cast, off)
+        return _build_mx_item(t, out_dtype, cast, off)
     src_esz = t.element_size()
     dst_esz = out_dtype.itemsize
     sizes, strides = collapse_layout(t)
@@ -407,14 +484,14 @@ def _build_cast_item(
     )
 
 
-def _build_mx_item(t: torch.Tensor, cast: int, off: int) -> PackItem:
-    """Descriptor of a tensor stored as, or restored from, block-scaled fp8.
-    The flat side is one code byte per element: ``nbytes`` is the codes
-    region, 32 bytes per block, and ``row_bytes`` the innermost run in
-    elements. ``vec`` names the kernel class: 8, four lanes per block with
-    16-byte tensor-side accesses, for a contiguous tensor or rows of 32k
-    elements whose base and strides are 16-byte aligned; 1, one lane per
-    block, for every other layout."""
+def _build_mx_item(t: torch.Tensor, stored: str, cast: int, off: int) -> PackItem:
+    """Descriptor of a tensor stored as, or restored from, the block-scaled
+    format ``stored``. ``nbytes`` is the codes region, 32 bytes per block for
+    fp8 (one code byte per element) and 16 for fp4 (two elements per byte),
+    and ``row_bytes`` the innermost run in elements. ``vec`` names the kernel
+    class: 8, four lanes per block with 16-byte tensor-side accesses, for a
+    contiguous tensor or rows of 32k elements whose base and strides are
+    16-byte aligned; 1, one lane per block, for every other layout."""
     esz = t.element_size()
     sizes, strides = collapse_layout(t)
     row_elems, outer_sizes, outer_strides_b, src_align = _layout_rows(
@@ -422,14 +499,15 @@ def _build_mx_item(t: torch.Tensor, cast: int, off: int) -> PackItem:
     )
     if src_align < esz:
         raise ValueError(
-            f"cannot stage a {t.dtype} tensor as {MXFP8_E4M3} whose address or "
+            f"cannot stage a {t.dtype} tensor as {stored} whose address or "
             f"strides are not {esz}-byte aligned"
         )
     aligned = src_align == 16 and (not outer_sizes or row_elems % MX_BLOCK == 0)
+    blocks = (t.numel() + MX_BLOCK - 1) // MX_BLOCK
     return PackItem(
         src_ptr=t.data_ptr(),
         flat_offset=off,
-        nbytes=(t.numel() + MX_BLOCK - 1) // MX_BLOCK * MX_BLOCK,
+        nbytes=mx_nbytes(t.numel(), stored) - blocks,  # all but the scales
         row_bytes=row_elems,
         outer_sizes=outer_sizes,
         outer_strides=outer_strides_b,
@@ -463,7 +541,7 @@ def build_scatter_items(
             # codes and scales move as 16-byte pieces; vec names the class
             if (flat_base + off) % 16:
                 raise ValueError(
-                    f"cannot decode {MXFP8_E4M3} from a payload at address "
+                    f"cannot decode {stored} from a payload at address "
                     f"{flat_base + off:#x}: not 16-byte aligned"
                 )
         elif it.nbytes:
@@ -517,7 +595,10 @@ def _scatter_layout_plan(
         return None
     if outer_dim_count(target) > MAX_OUTER_DIMS:
         return None
-    if stored_nbytes(target.numel(), stored_dtype) >= _KERNEL_MAX_BYTES:
+    # a block-scaled payload's elements are indexed in u32 as well, and fp4
+    # has more elements than bytes
+    span = target.numel() if is_mx(stored_dtype) else 0
+    if max(span, stored_nbytes(target.numel(), stored_dtype)) >= _KERNEL_MAX_BYTES:
         return None
     # torch strides are whole elements, so the base address decides whether
     # every element is aligned
@@ -1907,7 +1988,7 @@ class StagingEngine:
             if it.nbytes == 0:
                 continue
             if is_mx(out_dtype):
-                flat = mx_encode(t)
+                flat = mx_encode_as(t, out_dtype)
             else:
                 if it.cast != CAST_NONE:
                     t = t.to(out_dtype)

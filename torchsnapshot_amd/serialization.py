@@ -50,23 +50,36 @@ for _name in (
 _QUANTIZED_DTYPES = [torch.qint8, torch.quint8, torch.qint32]
 
 
-# block-scaled fp8 (docs/format.md): a stored format, not a torch dtype. It
-# is named by this string in save_dtype and in the manifest
+# block-scaled formats (docs/format.md): stored formats, not torch dtypes.
+# They are named by these strings in save_dtype and in the manifest
 MXFP8_E4M3 = "mxfp8_e4m3"
+MXFP4_E2M1 = "mxfp4_e2m1"
+
+# stored bytes per block of 32 elements: the codes and one scale byte
+_MX_BLOCK_BYTES = {MXFP8_E4M3: 33, MXFP4_E2M1: 17}
+
+
+def is_mx(dtype: Any) -> bool:
+    """Whether ``dtype`` (a torch.dtype, a string or None) names a
+    block-scaled stored format."""
+    return isinstance(dtype, str) and dtype in _MX_BLOCK_BYTES
+
+
+def mx_nbytes(numel: int, dtype: str) -> int:
+    """Payload bytes of ``numel`` elements in the block-scaled ``dtype``."""
+    return _MX_BLOCK_BYTES[dtype] * ((numel + 31) // 32)
 
 
 def dtype_to_str(dtype: Any) -> str:
-    if dtype == MXFP8_E4M3:
-        return MXFP8_E4M3
+    if is_mx(dtype):
+        return dtype
     return str(dtype).removeprefix("torch.")
 
 
 def entry_tensor_dtype(entry: Any) -> torch.dtype:
     """The dtype of the tensor a tensor or chunked entry holds: the logical
-    one when the payload is block-scaled fp8."""
-    return str_to_dtype(
-        entry.logical_dtype if entry.dtype == MXFP8_E4M3 else entry.dtype
-    )
+    one when the payload is block-scaled."""
+    return str_to_dtype(entry.logical_dtype if is_mx(entry.dtype) else entry.dtype)
 
 
 STR_TO_DTYPE = {dtype_to_str(d): d for d in _ALL_DTYPES + _QUANTIZED_DTYPES}

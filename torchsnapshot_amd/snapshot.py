@@ -66,7 +66,7 @@ from .manifest_ops import (
     get_manifest_for_rank,
     handle_sharded_tensor_elasticity,
 )
-from .serialization import MXFP8_E4M3
+from .serialization import MXFP4_E2M1, MXFP8_E4M3, is_mx
 from .partitioner import PartitionItem, partition_write_reqs
 from .pg_wrapper import PGWrapper
 from .rng_state import RNGState
@@ -115,7 +115,7 @@ def _match_segments(segs: List[str], pats: List[str]) -> bool:
 
 SaveDtype = Union[None, torch.dtype, str, Dict[str, Union[torch.dtype, str]]]
 
-_SAVE_DTYPE_TARGETS = (torch.bfloat16, torch.float16, MXFP8_E4M3)
+_SAVE_DTYPE_TARGETS = (torch.bfloat16, torch.float16, MXFP8_E4M3, MXFP4_E2M1)
 
 
 def _normalize_save_dtype(
@@ -125,14 +125,14 @@ def _normalize_save_dtype(
     rules; a bare dtype means {"**": dtype}. Raises before any I/O."""
     if save_dtype is None:
         return None
-    if isinstance(save_dtype, torch.dtype) or save_dtype == MXFP8_E4M3:
+    if isinstance(save_dtype, torch.dtype) or is_mx(save_dtype):
         rules = [("**", save_dtype)]
     elif isinstance(save_dtype, dict):
         rules = list(save_dtype.items())
     else:
         raise ValueError(
-            f"save_dtype must be a torch.dtype, {MXFP8_E4M3!r} or a dict of "
-            f"glob pattern -> either, got {save_dtype!r}"
+            f"save_dtype must be a torch.dtype, {MXFP8_E4M3!r}, {MXFP4_E2M1!r} "
+            f"or a dict of glob pattern -> any of these, got {save_dtype!r}"
         )
     for pattern, dtype in rules:
         if not isinstance(pattern, str):
@@ -140,7 +140,8 @@ def _normalize_save_dtype(
         if dtype not in _SAVE_DTYPE_TARGETS:
             raise ValueError(
                 f"save_dtype target {dtype!r} (pattern '{pattern}') is not "
-                f"supported; allowed: torch.bfloat16, torch.float16, {MXFP8_E4M3!r}"
+                "supported; allowed: torch.bfloat16, torch.float16, "
+                f"{MXFP8_E4M3!r}, {MXFP4_E2M1!r}"
             )
     return rules
 
@@ -153,8 +154,9 @@ def _resolve_save_dtype(
     """Stored dtype for one leaf, or None to store it unchanged. Only
     strided, non-quantized float32 tensors are narrowed (DTensor and
     ShardedTensor qualify through their local shards). The block-scaled
-    ``"mxfp8_e4m3"`` takes bfloat16 leaves as well, and plain tensors and
-    Parameters only: a sharded leaf its rule matches is stored as it is."""
+    ``"mxfp8_e4m3"`` and ``"mxfp4_e2m1"`` take bfloat16 leaves as well, and
+    plain tensors and Parameters only: a sharded leaf their rule matches is
+    stored as it is."""
     if not rules or not isinstance(obj, torch.Tensor):
         return None
     if obj.dtype not in (torch.float32, torch.bfloat16):
@@ -164,7 +166,7 @@ def _resolve_save_dtype(
         return None
     for pattern, dtype in rules:
         if glob_match(logical_path, pattern):
-            if dtype == MXFP8_E4M3:
+            if is_mx(dtype):
                 return dtype if plain else None
             return dtype if obj.dtype == torch.float32 else None
     return None
@@ -1118,9 +1120,9 @@ class Snapshot:
             if (plain_entry or entry.shape) and list(shape) != list(entry.shape):
                 sink.note(p, f"shape {tuple(entry.shape)} vs {tuple(shape)}")
                 continue
-            if plain_entry and entry.dtype == MXFP8_E4M3:
+            if plain_entry and is_mx(entry.dtype):
                 # lossy by design: the payload is not read at all
-                sink.note(p, f"stored as {MXFP8_E4M3}: not compared")
+                sink.note(p, f"stored as {entry.dtype}: not compared")
                 continue
             reqs, _ = prepare_read(entry, obj)
             _compare.attach_compare(reqs, sink, p, entry)

@@ -18,7 +18,7 @@ import torch
 
 from .flatten import flatten
 from .pg_wrapper import PGWrapper
-from .serialization import MXFP8_E4M3
+from .serialization import is_mx
 from .stateful import AppState
 
 POLICIES = ("ignore", "warn", "error")
@@ -78,9 +78,10 @@ class UniqueTensors:
         self.stored: List[Optional[torch.dtype]] = []
 
     def add(self, t: torch.Tensor, stored_dtype: Optional[torch.dtype]) -> int:
-        if stored_dtype == MXFP8_E4M3:
-            # the checks read live values under block-scaled fp8: quantising
-            # creates no Inf, and replicas are compared by their live bytes
+        if is_mx(stored_dtype):
+            # the checks read live values under a block-scaled format:
+            # quantising creates no Inf, and replicas are compared by their
+            # live bytes
             stored_dtype = None
         key: Any = len(self.tensors)  # sparse: no data_ptr, never aliased
         if t.layout == torch.strided and not t.is_quantized:
