@@ -23,6 +23,7 @@ DEPS = (
     SRC,
     PKG_ROOT / "ops" / "hip" / "desc_check.h",
     PKG_ROOT / "ops" / "hip" / "file_sink.h",
+    PKG_ROOT / "ops" / "hip" / "mx_codec.h",
     PKG_ROOT / "ops" / "hip" / "table_ring.h",
     Path(__file__).resolve(),  # the compiler flags
 )

@@ -24,6 +24,8 @@
 #include <string>
 #include <vector>
 
+#include "mx_codec.h"
+
 namespace tsamd {
 
 constexpr int kMaxDims = 6;
@@ -78,26 +80,27 @@ constexpr uint32_t kCastF32toMX = 16;   // gather
 constexpr uint32_t kCastBF16toMX = 17;  // gather
 constexpr uint32_t kCastMXtoF32 = 18;   // scatter
 constexpr uint32_t kCastMXtoBF16 = 19;  // scatter
-constexpr uint32_t kMxBlock = 32;      // elements per scale byte
 // block-scaled fp4 (mxfp4_e2m1): two elements per code byte
 constexpr uint32_t kCastF32toMX4 = 20;   // gather
 constexpr uint32_t kCastBF16toMX4 = 21;  // gather
 constexpr uint32_t kCastMX4toF32 = 22;   // scatter
 constexpr uint32_t kCastMX4toBF16 = 23;  // scatter
-constexpr uint32_t kMx4BlockBytes = kMxBlock / 2;  // code bytes per block
 
 constexpr bool is_mx_cast(uint32_t code) { return code >= kCastF32toMX; }
-constexpr bool is_mx4_cast(uint32_t code) { return code >= kCastF32toMX4; }
-// tensor-side element size of an mx descriptor
-constexpr uint32_t mx_elem_size(uint32_t code) {
-  return (code == kCastF32toMX || code == kCastMXtoF32 ||
-          code == kCastF32toMX4 || code == kCastMX4toF32)
-             ? 4u
-             : 2u;
+// tensor-side element size of an mx descriptor: in both directions and both
+// formats the odd code is the bf16 one
+constexpr uint32_t mx_elem_size(uint32_t code) { return code & 1u ? 2u : 4u; }
+
+// What check_descs needs to know of an mx descriptor's format (mx_codec.h):
+// the code bytes of a block, and the name its refusals carry
+struct MxBlockRule {
+  uint32_t block_bytes;
+  const char* tag;
+};
+constexpr MxBlockRule mx_block_rule(uint32_t code) {
+  return code >= kCastF32toMX4 ? MxBlockRule{MxFp4E2M1::kBlockBytes, "mx4: "}
+                               : MxBlockRule{MxFp8E4M3::kBlockBytes, "mx: "};
 }
-// Largest codes region of an mxfp4 descriptor: a code byte is two elements,
-// and the kernels index elements in u32 like everything else
-constexpr uint32_t kMaxMx4CodeBytes = kMaxDescBytes / 2;
 
 // element classes of the non-finite scan (SCAN_* in ops/staging.py)
 constexpr uint32_t kScanF64 = 0;
@@ -304,17 +307,18 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
     }
     const uint32_t v = d.vec;
     if (is_mx_cast(d.cast)) {
-      // Block-scaled fp8 and fp4: only Gather and Unpack let these codes
+      // Block-scaled formats: only Gather and Unpack let these codes
       // through. The rules are the accesses mx_gather_* and mx_scatter_*
-      // (mx4_* for fp4) make; fp4 differs in the code bytes per block and
-      // in its size cap.
-      const bool fp4 = is_mx4_cast(d.cast);
-      const uint32_t bb = fp4 ? kMx4BlockBytes : kMxBlock;
+      // make; a format enters through its code bytes per block.
+      const MxBlockRule rule = mx_block_rule(d.cast);
+      const uint32_t bb = rule.block_bytes;
       auto refuse_mx = [&](const char* what) {
-        refuse(((fp4 ? "mx4: " : "mx: ") + std::string(what)).c_str());
+        refuse((rule.tag + std::string(what)).c_str());
       };
       if (d.nbytes % bb != 0) refuse_mx("nbytes must be whole blocks");
-      if (fp4 && d.nbytes > kMaxMx4CodeBytes) {
+      // the kernels index elements in u32 like everything else, and a code
+      // byte may hold more than one (at one per byte this is the cap above)
+      if (d.nbytes > kMaxDescBytes / kMxBlock * bb) {
         refuse_mx("too many elements (> 2^32 - 64 Ki)");
       }
       if (v != 8 && v != 1) refuse_mx("vec must be 8 (aligned) or 1 (general)");
@@ -324,7 +328,7 @@ inline void check_descs(const std::vector<Desc>& descs, DescKind kind,
       if ((n + kMxBlock - 1) / kMxBlock * bb != d.nbytes) {
         refuse_mx("nbytes is not the block-padded element count");
       }
-      // codes go as 8 B (fp4: 4 B) and 16 B accesses, scales as 16 B ones
+      // codes go as 8 B or 4 B and as 16 B accesses, scales as 16 B ones
       if (d.flat_off % 16 != 0) refuse_mx("flat offset must be 16-aligned");
       if (flat != nullptr) {
         const uintptr_t base =

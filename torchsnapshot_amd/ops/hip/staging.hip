@@ -11,6 +11,9 @@
 //     the same launch (save_dtype), so only stored-size bytes leave the GPU
 //   - scatter kernel for restore (and for scatter_h2d), with bf16/f16 ->
 //     f32 widening and the psum64 check fused into the launch
+//   - block-scaled saves (mxfp8_e4m3, mxfp4_e2m1): one set of gather and
+//     scatter routes over the format structs and bit arithmetic of
+//     mx_codec.h, in a gather and a scatter kernel of their own
 //   - scan kernel: NaN / Inf counts per tensor over the same descriptors,
 //     read-only, one launch for the whole state (the nonfinite= policy)
 //   - fingerprint kernel: the psum64 of each tensor's stored bytes, read in
@@ -478,6 +481,30 @@ __device__ unsigned long long cast_range(const Desc& d, char* flat_base,
   return h;
 }
 
+// One plain or cast descriptor's work unit of the gather, by its vec. Only
+// CAST instantiations hold the cast route.
+template <bool HASH, bool CAST>
+__device__ __forceinline__ unsigned long long pack_unit(const Desc& d,
+                                                        char* flat_base,
+                                                        uint32_t s,
+                                                        uint32_t e) {
+  if (CAST && d.cast != kCastNone) {
+    switch (d.vec) {
+      case 16: return cast_range<16, HASH>(d, flat_base, s, e);
+      case 8: return cast_range<8, HASH>(d, flat_base, s, e);
+      case 4: return cast_range<4, HASH>(d, flat_base, s, e);
+      default: return cast_range<2, HASH>(d, flat_base, s, e);
+    }
+  }
+  switch (d.vec) {
+    case 16: return gather_range<16, HASH>(d, flat_base, s, e);
+    case 8: return gather_range<8, HASH>(d, flat_base, s, e);
+    case 4: return gather_range<4, HASH>(d, flat_base, s, e);
+    case 2: return gather_range<2, HASH>(d, flat_base, s, e);
+    default: return gather_range<1, HASH>(d, flat_base, s, e);
+  }
+}
+
 // Gather kernel; when HASH, hash_out[i] accumulates the psum64 of
 // descriptor i's bytes at slab offsets. CAST instantiations additionally
 // route descriptors with a cast code to cast_range; they are launched only
@@ -491,23 +518,7 @@ __global__ __launch_bounds__(kBlockThreads) void pack_kernel(
   for_each_work_unit(
       descs, n, wu_prefix, total_wus,
       [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
-        unsigned long long h = 0;
-        if (CAST && d.cast != kCastNone) {
-          switch (d.vec) {
-            case 16: h = cast_range<16, HASH>(d, flat_base, s, e); break;
-            case 8: h = cast_range<8, HASH>(d, flat_base, s, e); break;
-            case 4: h = cast_range<4, HASH>(d, flat_base, s, e); break;
-            default: h = cast_range<2, HASH>(d, flat_base, s, e); break;
-          }
-        } else {
-          switch (d.vec) {
-            case 16: h = gather_range<16, HASH>(d, flat_base, s, e); break;
-            case 8: h = gather_range<8, HASH>(d, flat_base, s, e); break;
-            case 4: h = gather_range<4, HASH>(d, flat_base, s, e); break;
-            case 2: h = gather_range<2, HASH>(d, flat_base, s, e); break;
-            default: h = gather_range<1, HASH>(d, flat_base, s, e); break;
-          }
-        }
+        const unsigned long long h = pack_unit<HASH, CAST>(d, flat_base, s, e);
         if (HASH) add_per_wave(&hash_out[owner], h);
       });
 }
@@ -614,6 +625,29 @@ __device__ unsigned long long widen_range(const Desc& d,
   return h;
 }
 
+// One plain or cast descriptor's work unit of the scatter, by its vec. Only
+// WIDEN instantiations hold the widening route.
+template <bool HASH, bool WIDEN>
+__device__ __forceinline__ unsigned long long unpack_unit(
+    const Desc& d, const char* fb, uint32_t s, uint32_t e,
+    unsigned long long ho) {
+  if (WIDEN && d.cast != kCastNone) {
+    switch (d.vec) {
+      case 16: return widen_range<16, HASH>(d, fb, s, e, ho);
+      case 8: return widen_range<8, HASH>(d, fb, s, e, ho);
+      case 4: return widen_range<4, HASH>(d, fb, s, e, ho);
+      default: return widen_range<2, HASH>(d, fb, s, e, ho);
+    }
+  }
+  switch (d.vec) {
+    case 16: return scatter_range<16, HASH>(d, fb, s, e, ho);
+    case 8: return scatter_range<8, HASH>(d, fb, s, e, ho);
+    case 4: return scatter_range<4, HASH>(d, fb, s, e, ho);
+    case 2: return scatter_range<2, HASH>(d, fb, s, e, ho);
+    default: return scatter_range<1, HASH>(d, fb, s, e, ho);
+  }
+}
+
 // Scatter kernel (restore, and scatter_h2d): flat bytes into strided
 // device tensors, widening when WIDEN; when HASH, hash_out[i] accumulates
 // the psum64 of descriptor i's flat bytes at file offset hash_byte0 +
@@ -631,128 +665,67 @@ __global__ __launch_bounds__(kBlockThreads) void unpack_kernel(
   for_each_work_unit(
       descs, n, wu_prefix, total_wus,
       [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
-        const unsigned long long ho = hash_byte0 + d.flat_off;
-        const char* fb = flat_base;
-        unsigned long long h = 0;
-        if (WIDEN && d.cast != kCastNone) {
-          switch (d.vec) {
-            case 16: h = widen_range<16, HASH>(d, fb, s, e, ho); break;
-            case 8: h = widen_range<8, HASH>(d, fb, s, e, ho); break;
-            case 4: h = widen_range<4, HASH>(d, fb, s, e, ho); break;
-            default: h = widen_range<2, HASH>(d, fb, s, e, ho); break;
-          }
-        } else {
-          switch (d.vec) {
-            case 16: h = scatter_range<16, HASH>(d, fb, s, e, ho); break;
-            case 8: h = scatter_range<8, HASH>(d, fb, s, e, ho); break;
-            case 4: h = scatter_range<4, HASH>(d, fb, s, e, ho); break;
-            case 2: h = scatter_range<2, HASH>(d, fb, s, e, ho); break;
-            default: h = scatter_range<1, HASH>(d, fb, s, e, ho); break;
-          }
-        }
+        const unsigned long long h = unpack_unit<HASH, WIDEN>(
+            d, flat_base, s, e, hash_byte0 + d.flat_off);
         if (HASH) add_per_wave(&hash_out[owner], h);
       });
 }
 
 // ---------------------------------------------------------------------------
-// block-scaled fp8 (mxfp8_e4m3; docs/format.md): 32 elements share one
-// power-of-two scale byte X = E + 127 (E8M0), each element is one e4m3fn
-// code of x * 2^-E. A payload is [codes: 32*nb bytes][scales: nb bytes].
-// The descriptor's flat range is the codes region, one byte per element,
-// so a 64 KiB work unit is 2048 blocks and owns 2048 scale bytes at
-// flat_off + nbytes + s / 32.
+// block-scaled saves (mxfp8_e4m3 and mxfp4_e2m1; docs/format.md): 32
+// elements share one power-of-two scale byte X = E + 127 (E8M0), each
+// element is one code of x * 2^-E. A payload is [codes: B*nb bytes][scales:
+// nb bytes], B = FMT::kBlockBytes code bytes per block. The descriptor's flat
+// range is the codes region, so a 64 KiB work unit is 65536 / B blocks and
+// owns that many scale bytes at flat_off + nbytes + s / B. The formats are
+// the structs of mx_codec.h, which also holds the bit arithmetic; every
+// route below is one template over them.
 //
 //   - aligned class (vec 8: contiguous tensors, and rows of 32k elements
 //     with a 16 B aligned tensor side): lanes run across the unit, 8
 //     elements each: one 16 B load of bf16 or two of f32. The four lanes of
 //     a block reduce amax on the bit patterns (the order of non-negative
 //     floats is the order of their patterns) with two xor shuffles; a block
-//     never crosses a wave. Each lane converts its 8 elements and stores 8
-//     code bytes, 512 contiguous bytes per wave
-//   - general class (vec 1: every other layout): one lane per block; it
-//     walks the block's 32 elements, taking row_offset again at each row
-//     boundary, keeps them in a per-lane array and stores the codes as two
-//     16 B pieces
+//     never crosses a wave. Each lane converts its 8 elements and stores
+//     their code bytes in one piece
+//   - general class (vec 1: every other layout): one lane per block, two
+//     passes over its elements, taking row_offset again at each row
+//     boundary: the first takes amax, the second reads them again (from
+//     cache) and encodes them dword by dword. The loops over a block's
+//     pieces, dwords and codes have constant trip counts and nothing is
+//     indexed at run time, so the block never sits in private memory; the
+//     codes leave as 16 B stores. (fp8 alone walks once and keeps the block
+//     in registers, see mx_gather_general.) The scatter loads a block's
+//     codes as 16 B pieces and walks the rows once
 //   - scales never leave as single bytes (in direct mode the flat side is
 //     pinned host memory across PCIe): the unit's scale bytes are collected
-//     in 2 KiB of LDS and, after a workgroup barrier, written as 16 B
-//     pieces; only the payload's last, short piece goes narrower. The
-//     scatter mirrors this: it first loads the unit's scales into LDS with
-//     16 B loads (the flat side is read exactly once), then decodes. The
-//     buffer is sized for fp4's units below, 4096 blocks and 4 KiB
-//   - conversion is integer arithmetic on the bit patterns, like the casts
-//     above: f32 subnormals, e4m3 subnormals and ties come out the same in
-//     every wave mode. A bf16 source is its f32 pattern (<< 16)
+//     in LDS and, after a workgroup barrier, written as 16 B pieces; only
+//     the payload's last, short piece goes narrower. The scatter mirrors
+//     this: it first loads the unit's scales into LDS with 16 B loads (the
+//     flat side is read exactly once), then decodes
 //   - psum64: codes are hashed from the registers stored (or loaded), scales
 //     where they leave (enter) LDS, at their own payload offsets
 //   - the kernels below also run plain and cast descriptors, so a slab may
-//     mix all three; they are launched only for batches that hold an mx
+//     mix all of them; they are launched only for batches that hold an mx
 //     descriptor, and pack_kernel / unpack_kernel stay as they were
+//
+// What a format changes, and nothing else:
+//   - mxfp8_e4m3: B = 32, a unit is 2048 blocks. A lane of the aligned class
+//     stores 8 code bytes, a wave 512 contiguous bytes; a block of the
+//     general class is two 16 B pieces. The codes carry NaN themselves
+//   - mxfp4_e2m1: B = 16, two codes per byte, element 2j of a block in the
+//     low nibble of its byte j; a unit is 4096 blocks (131072 elements),
+//     which sizes the LDS buffer at 4 KiB. A lane of the aligned class packs
+//     its eight nibbles into one dword, a wave stores 256 contiguous bytes;
+//     a block of the general class is one 16 B piece. e2m1 has no NaN and
+//     no Inf: a block with a non-finite element stores X = 0xFF (the whole
+//     block decodes to NaN), its non-finite elements magnitude 7. Whether a
+//     block has one is a ballot over its four lanes
 // ---------------------------------------------------------------------------
 
-constexpr uint32_t kMxUnitBlocks = kWorkUnitBytes / kMxBlock;  // 2048
-
-// E of a block from the pattern of its amax (finite, sign cleared):
-// floor(log2 amax) - 8, one more when amax * 2^-E would exceed 448 =
-// 1.75 * 2^8, at least -127. Zero and f32 subnormals end at -127.
-__device__ __host__ inline int mx_block_exp(uint32_t amax) {
-  if (amax < 0x00800000u) return -127;
-  const int e = (int)(amax >> 23) - 135 + ((amax & 0x007FFFFFu) > 0x00600000u);
-  return e < -127 ? -127 : e;
-}
-
-// e4m3fn code of the f32 pattern u scaled by 2^-E, round to nearest even,
-// clamped to +-448; NaN and +-Inf become the NaN code with the sign kept.
-__device__ __host__ inline uint32_t mx_code(uint32_t u, int E) {
-  const uint32_t sign = (u >> 24) & 0x80u;
-  const uint32_t a = u & 0x7FFFFFFFu;
-  if (a >= 0x7F800000u) return sign | 0x7Fu;
-  if (a == 0u) return sign;
-  // |x| = M * 2^(ex - 23) with M in [2^23, 2^24)
-  uint32_t M = a & 0x007FFFFFu;
-  int ex = (int)(a >> 23) - 127;
-  if (a < 0x00800000u) {
-    const int lz = __builtin_clz(M) - 8;  // 1..23
-    M <<= lz;
-    ex = -126 - lz;
-  } else {
-    M |= 0x00800000u;
-  }
-  // y = |x| * 2^-E has exponent t. From t = -6 up it is an e4m3 normal with
-  // step 2^(t-3): q = RNE(M / 2^20) in [8, 16], and a carry to 16 runs into
-  // the exponent field. Below, the step stays 2^-9 (e4m3 subnormals).
-  const int t = ex - E;
-  const int shift = 20 + (t < -6 ? -6 - t : 0);
-  const uint32_t sh = shift > 26 ? 26u : (uint32_t)shift;  // >= 25 gives 0
-  const uint32_t q = (M + ((1u << (sh - 1)) - 1u) + ((M >> sh) & 1u)) >> sh;
-  const uint32_t code = t >= -6 ? ((uint32_t)(t + 6) << 3) + q : q;
-  return sign | (code > 0x7Eu ? 0x7Eu : code);
-}
-
-// f32 pattern of e4m3fn(code) * 2^(X - 127): exact, f32 subnormals included
-__device__ __host__ inline uint32_t mx_decode_bits(uint32_t c, uint32_t X) {
-  const uint32_t sign = (c & 0x80u) << 24;
-  const uint32_t a = c & 0x7Fu;
-  if (a == 0x7Fu || X == 0xFFu) return sign | 0x7FC00000u;
-  if (a == 0u) return sign;
-  const uint32_t ef = a >> 3, m = a & 7u;
-  int ex;
-  uint32_t frac;
-  if (ef != 0u) {
-    ex = (int)ef - 7;
-    frac = m << 20;
-  } else {
-    const int p = 31 - __builtin_clz(m);  // 0..2
-    ex = p - 9;
-    frac = (m << (23 - p)) & 0x007FFFFFu;
-  }
-  const int biased = ex + (int)X;  // ex + (X - 127) + 127
-  if (biased >= 255) return sign | 0x7F800000u;
-  if (biased > 0) return sign | ((uint32_t)biased << 23) | frac;
-  // only the top four bits of the significand are set and the shift is at
-  // most 10: nothing is lost
-  return sign | ((0x00800000u | frac) >> (1 - biased));
-}
+// the most blocks a work unit holds in any format: the LDS scale buffer
+constexpr uint32_t kMxUnitBlocks = kWorkUnitBytes / MxFp4E2M1::kBlockBytes;
+static_assert(MxFp8E4M3::kBlockBytes >= MxFp4E2M1::kBlockBytes);
 
 __device__ __forceinline__ unsigned long long psum_piece(
     unsigned long long v, unsigned long long file_off) {
@@ -761,7 +734,7 @@ __device__ __forceinline__ unsigned long long psum_piece(
 }
 
 // 8 consecutive source elements as f32 patterns; the ones from `valid` on do
-// not exist and read as +0
+// not exist and read as +0. A bf16 source is its f32 pattern (<< 16)
 template <bool BF16>
 __device__ __forceinline__ void mx_load8(const char* src, uint32_t valid,
                                          uint32_t (&v)[8]) {
@@ -789,15 +762,13 @@ __device__ __forceinline__ void mx_load8(const char* src, uint32_t valid,
   }
 }
 
-// amax pattern of one element: non-finite elements do not exist for it
-__device__ __forceinline__ uint32_t mx_amax_of(uint32_t u) {
-  const uint32_t a = u & 0x7FFFFFFFu;
-  return a < 0x7F800000u ? a : 0u;
+__device__ __forceinline__ bool mx_nonfinite(uint32_t u) {
+  return (u & 0x7FFFFFFFu) >= 0x7F800000u;
 }
 
-__device__ __forceinline__ uint32_t mx_code4(const uint32_t* v, int E) {
-  return mx_code(v[0], E) | (mx_code(v[1], E) << 8) | (mx_code(v[2], E) << 16) |
-         (mx_code(v[3], E) << 24);
+// amax pattern of one element: non-finite elements do not exist for it
+__device__ __forceinline__ uint32_t mx_amax_of(uint32_t u) {
+  return mx_nonfinite(u) ? 0u : u & 0x7FFFFFFFu;
 }
 
 // where element i of an aligned-class tensor sits, and how many of the 8
@@ -818,34 +789,86 @@ __device__ __forceinline__ const char* mx_aligned_addr(const Desc& d,
   return d.tensor_base + row_offset(d, row) + (unsigned long long)TS * col;
 }
 
+// The aligned class's lane piece: the codes of a lane's 8 elements are
+// FMT::kBits bytes, stored (and loaded) as one naturally aligned piece, a
+// uint2 or a dword. When HASH, `h` takes its psum64 contribution.
+template <typename FMT, bool HASH>
+__device__ __forceinline__ void mx_store_lane(char* flat,
+                                              const uint32_t (&c)[2],
+                                              unsigned long long file_off,
+                                              unsigned long long& h) {
+  if constexpr (FMT::kBits == 8) {
+    *reinterpret_cast<uint2*>(flat) = make_uint2(c[0], c[1]);
+    if (HASH) {
+      h += (((unsigned long long)c[1] << 32) | c[0]) * psum_mult(file_off >> 3);
+    }
+  } else {
+    static_assert(FMT::kBits == 4, "a lane's codes are a uint2 or a dword");
+    *reinterpret_cast<uint32_t*>(flat) = c[0];
+    if (HASH) h += psum_piece(c[0], file_off);
+  }
+}
+
+template <typename FMT, bool HASH>
+__device__ __forceinline__ void mx_load_lane(const char* flat, uint32_t (&c)[2],
+                                             unsigned long long file_off,
+                                             unsigned long long& h) {
+  if constexpr (FMT::kBits == 8) {
+    const uint2 a = *reinterpret_cast<const uint2*>(flat);
+    c[0] = a.x;
+    c[1] = a.y;
+    if (HASH) {
+      h += (((unsigned long long)c[1] << 32) | c[0]) * psum_mult(file_off >> 3);
+    }
+  } else {
+    static_assert(FMT::kBits == 4, "a lane's codes are a uint2 or a dword");
+    c[0] = *reinterpret_cast<const uint32_t*>(flat);
+    c[1] = 0u;
+    if (HASH) h += psum_piece(c[0], file_off);
+  }
+}
+
 // Aligned gather of [s, e) of the codes region of one work unit; the unit's
 // scale bytes go to `lds`.
-template <bool BF16, bool HASH>
+template <typename FMT, bool BF16, bool HASH>
 __device__ unsigned long long mx_gather_aligned(const Desc& d, char* flat_base,
                                                 uint32_t s, uint32_t e,
                                                 unsigned char* lds) {
+  constexpr uint32_t LB = FMT::kBits;        // code bytes of 8 elements
+  constexpr uint32_t CPW = 32 / FMT::kBits;  // codes per dword
   char* flat = flat_base + d.flat_off;
   unsigned long long h = 0;
-  for (uint32_t i = s + threadIdx.x * 8; i < e; i += kBlockThreads * 8) {
+  for (uint32_t i = s + threadIdx.x * LB; i < e; i += kBlockThreads * LB) {
     uint32_t valid;
-    const char* src = mx_aligned_addr<BF16 ? 2 : 4>(d, i, valid);
+    const char* src = mx_aligned_addr<BF16 ? 2 : 4>(d, i * (8 / LB), valid);
     uint32_t v[8];
     mx_load8<BF16>(src, valid, v);
     uint32_t amax = 0;
+    bool nonfinite = false;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) amax = max(amax, mx_amax_of(v[k]));
+    for (int k = 0; k < 8; ++k) {
+      amax = max(amax, mx_amax_of(v[k]));
+      nonfinite = nonfinite || mx_nonfinite(v[k]);
+    }
     // e and the unit are whole blocks: the four lanes of a block are all
     // here or all gone
     amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
     amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2, 64));
-    const int E = mx_block_exp(amax);
-    const uint2 o = make_uint2(mx_code4(v, E), mx_code4(v + 4, E));
-    *reinterpret_cast<uint2*>(flat + i) = o;
-    if (HASH) {
-      h += (((unsigned long long)o.y << 32) | o.x) *
-           psum_mult((d.flat_off + i) >> 3);
+    const int E = mx_block_exp<FMT>(amax);
+    uint32_t X = (uint32_t)(E + 127);
+    if constexpr (!FMT::kHasNan) {
+      // the codes cannot say NaN, the block's scale byte does
+      if (((__ballot(nonfinite) >> (threadIdx.x & 60u)) & 0xFull) != 0) X = 0xFFu;
     }
-    if ((threadIdx.x & 3u) == 0u) lds[(i - s) >> 5] = (unsigned char)(E + 127);
+    uint32_t c[2] = {0u, 0u};
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) {
+      c[k / CPW] |= mx_encode<FMT>(v[k], E) << (FMT::kBits * (k % CPW));
+    }
+    mx_store_lane<FMT, HASH>(flat + i, c, d.flat_off + i, h);
+    if ((threadIdx.x & 3u) == 0u) {
+      lds[(i - s) / FMT::kBlockBytes] = (unsigned char)X;
+    }
   }
   return h;
 }
@@ -857,49 +880,99 @@ __device__ __forceinline__ uint32_t mx_numel(const Desc& d) {
   return n;
 }
 
-// General gather: one lane per block, walking rows.
-template <bool BF16, bool HASH>
+// The general class's walk: the f32 pattern of the element at (p, col), then
+// one step on in row-major order; `more` is false at the tensor's last element
+template <bool BF16>
+__device__ __forceinline__ uint32_t mx_walk_load(const Desc& d, const char*& p,
+                                                 uint32_t& row, uint32_t& col,
+                                                 bool more) {
+  const char* q = p + (unsigned long long)(BF16 ? 2 : 4) * col;
+  const uint32_t u = BF16 ? (uint32_t)*reinterpret_cast<const uint16_t*>(q) << 16
+                          : *reinterpret_cast<const uint32_t*>(q);
+  if (++col == d.row_bytes && more) {
+    col = 0;
+    p = d.tensor_base + row_offset(d, ++row);
+  }
+  return u;
+}
+
+// General gather: one lane per block, walking rows twice. The one place where
+// the formats choose differently, by measurement
+// (profiles/mx_codec_refactor_measurements.md): fp8 walks once and keeps the
+// block's elements in registers between the amax and the encoding, which is
+// 4 % faster for it on strided reads and sets the register count of both mx
+// kernels; fp4 reads its elements twice.
+template <typename FMT, bool BF16, bool HASH>
 __device__ unsigned long long mx_gather_general(const Desc& d, char* flat_base,
                                                 uint32_t s, uint32_t e,
                                                 unsigned char* lds) {
-  constexpr int TS = BF16 ? 2 : 4;
+  constexpr uint32_t BB = FMT::kBlockBytes;
+  constexpr uint32_t CPW = 32 / FMT::kBits;  // codes per dword
+  constexpr bool KEEP = FMT::kBits == 8;
   char* flat = flat_base + d.flat_off;
-  const uint32_t rb = d.row_bytes;
   const uint32_t n = mx_numel(d);
   unsigned long long h = 0;
-  for (uint32_t i0 = s + threadIdx.x * kMxBlock; i0 < e;
-       i0 += kBlockThreads * kMxBlock) {
-    uint32_t row = i0 / rb;
-    uint32_t col = i0 - row * rb;
-    const char* p = d.tensor_base + row_offset(d, row);
-    uint32_t v[kMxBlock];
+  for (uint32_t i0 = s + threadIdx.x * BB; i0 < e; i0 += kBlockThreads * BB) {
+    // the block's first element exists: nbytes is ceil(n / 32) blocks
+    const uint32_t el0 = i0 * (8 / FMT::kBits);
+    const uint32_t count = min(n - el0, kMxBlock);
+    const uint32_t row0 = el0 / d.row_bytes;
+    const uint32_t col0 = el0 - row0 * d.row_bytes;
+    const char* const p0 = d.tensor_base + row_offset(d, row0);
+
+    uint32_t row = row0, col = col0;
+    const char* p = p0;
     uint32_t amax = 0;
+    bool nonfinite = false;
+    uint32_t v[KEEP ? kMxBlock : 1];
+    if constexpr (KEEP) {
 #pragma unroll
-    for (uint32_t j = 0; j < kMxBlock; ++j) {
-      v[j] = 0u;
-      if (i0 + j < n) {
-        const char* q = p + (unsigned long long)TS * col;
-        v[j] = BF16 ? (uint32_t)*reinterpret_cast<const uint16_t*>(q) << 16
-                    : *reinterpret_cast<const uint32_t*>(q);
-        if (++col == rb && i0 + j + 1 < n) {
-          col = 0;
-          p = d.tensor_base + row_offset(d, ++row);
+      for (uint32_t j = 0; j < kMxBlock; ++j) {
+        v[j] = 0u;
+        if (j < count) v[j] = mx_walk_load<BF16>(d, p, row, col, j + 1 < count);
+        amax = max(amax, mx_amax_of(v[j]));
+        nonfinite = nonfinite || mx_nonfinite(v[j]);
+      }
+    } else {
+      for (uint32_t j = 0; j < count; ++j) {
+        const uint32_t u = mx_walk_load<BF16>(d, p, row, col, j + 1 < count);
+        amax = max(amax, mx_amax_of(u));
+        nonfinite = nonfinite || mx_nonfinite(u);
+      }
+      row = row0, col = col0, p = p0;
+    }
+    const int E = mx_block_exp<FMT>(amax);
+
+    // constant trip counts, so that `o` stays in registers
+    uint4 o[BB / 16];
+#pragma unroll
+    for (uint32_t piece = 0; piece < BB / 16; ++piece) {
+      uint32_t w[4];
+#pragma unroll
+      for (uint32_t q = 0; q < 4; ++q) {
+        w[q] = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < CPW; ++k) {
+          const uint32_t j = (4 * piece + q) * CPW + k;
+          if constexpr (KEEP) {
+            w[q] |= mx_encode<FMT>(v[j], E) << (FMT::kBits * k);
+          } else if (j < count) {
+            const uint32_t u = mx_walk_load<BF16>(d, p, row, col, j + 1 < count);
+            w[q] |= mx_encode<FMT>(u, E) << (FMT::kBits * k);
+          }
         }
       }
-      amax = max(amax, mx_amax_of(v[j]));
+      o[piece] = make_uint4(w[0], w[1], w[2], w[3]);
     }
-    const int E = mx_block_exp(amax);
-    const uint4 a = make_uint4(mx_code4(v, E), mx_code4(v + 4, E),
-                               mx_code4(v + 8, E), mx_code4(v + 12, E));
-    const uint4 b = make_uint4(mx_code4(v + 16, E), mx_code4(v + 20, E),
-                               mx_code4(v + 24, E), mx_code4(v + 28, E));
-    *reinterpret_cast<uint4*>(flat + i0) = a;
-    *reinterpret_cast<uint4*>(flat + i0 + 16) = b;
-    if (HASH) {
-      h += psum_regs<16>(a, d.flat_off + i0) +
-           psum_regs<16>(b, d.flat_off + i0 + 16);
+    // a block's pieces leave together: across PCIe two halves of a 32 B run
+    // stored far apart in time are two partial writes
+#pragma unroll
+    for (uint32_t piece = 0; piece < BB / 16; ++piece) {
+      *reinterpret_cast<uint4*>(flat + i0 + 16 * piece) = o[piece];
+      if (HASH) h += psum_regs<16>(o[piece], d.flat_off + i0 + 16 * piece);
     }
-    lds[(i0 - s) >> 5] = (unsigned char)(E + 127);
+    lds[(i0 - s) / BB] = !FMT::kHasNan && nonfinite ? 0xFFu
+                                                    : (unsigned char)(E + 127);
   }
   return h;
 }
@@ -955,226 +1028,32 @@ __device__ unsigned long long mx_move_scales(char* payload, unsigned char* lds,
 }
 
 // One mx descriptor's work unit of the gather: codes, then the scales.
-template <bool HASH>
+template <typename FMT, bool BF16, bool HASH>
 __device__ unsigned long long mx_gather_unit(const Desc& d, char* flat_base,
                                              uint32_t s, uint32_t e,
                                              unsigned char* lds) {
-  const bool bf16 = d.cast == kCastBF16toMX;
-  unsigned long long h;
-  if (d.vec == 8) {
-    h = bf16 ? mx_gather_aligned<true, HASH>(d, flat_base, s, e, lds)
-             : mx_gather_aligned<false, HASH>(d, flat_base, s, e, lds);
-  } else {
-    h = bf16 ? mx_gather_general<true, HASH>(d, flat_base, s, e, lds)
-             : mx_gather_general<false, HASH>(d, flat_base, s, e, lds);
-  }
-  const unsigned long long scales_off = d.flat_off + d.nbytes + (s >> 5);
+  const unsigned long long h =
+      d.vec == 8 ? mx_gather_aligned<FMT, BF16, HASH>(d, flat_base, s, e, lds)
+                 : mx_gather_general<FMT, BF16, HASH>(d, flat_base, s, e, lds);
+  const unsigned long long scales_off =
+      d.flat_off + d.nbytes + s / FMT::kBlockBytes;
   return h + mx_move_scales<true, HASH>(flat_base + scales_off, lds,
-                                        (e - s) >> 5, scales_off);
+                                        (e - s) / FMT::kBlockBytes, scales_off);
 }
 
-// ---------------------------------------------------------------------------
-// block-scaled fp4 (mxfp4_e2m1; docs/format.md): the same payload with two
-// e2m1 codes per byte, [codes: 16*nb bytes][scales: nb bytes]; element 2j of
-// a block is the low nibble of its byte j. The descriptor's flat range is
-// again the codes region, so a 64 KiB work unit is 4096 blocks (131072
-// elements) and owns 4096 scale bytes at flat_off + nbytes + s / 16.
-//
-//   - aligned class: four lanes per block as above, 8 elements each; a lane
-//     packs its eight nibbles into one dword, 256 contiguous bytes per wave
-//   - general class: one lane per block, two passes over its elements: the
-//     first takes amax, the second reads them again (from cache) and encodes
-//     eight at a time into one dword. Nothing is indexed at run time, so the
-//     block never sits in private memory; the 16 code bytes leave as one
-//     16 B store
-//   - e2m1 has no NaN and no Inf: a block with a non-finite element stores
-//     X = 0xFF (the whole block decodes to NaN), its non-finite elements
-//     magnitude 7. Whether a block has one is a ballot over its four lanes
-//   - scales, psum64 and mixing with other descriptors: as for fp8
-// ---------------------------------------------------------------------------
-
-constexpr uint32_t kMx4UnitBlocks = kWorkUnitBytes / kMx4BlockBytes;  // 4096
-
-// E of a block from the pattern of its amax (finite, sign cleared):
-// floor(log2 amax) - 2, one more when amax * 2^-E would exceed 6 = 1.5 * 2^2,
-// at least -127. Zero and f32 subnormals end at -127.
-__device__ __host__ inline int mx4_block_exp(uint32_t amax) {
-  if (amax < 0x00800000u) return -127;
-  const int e = (int)(amax >> 23) - 129 + ((amax & 0x007FFFFFu) > 0x00400000u);
-  return e < -127 ? -127 : e;
-}
-
-// e2m1 code (4 bits) of the f32 pattern u scaled by 2^-E, round to nearest
-// even on the grid 0, 0.5, 1, 1.5, 2, 3, 4, 6, clamped to +-6; NaN and +-Inf
-// become magnitude 7 with the sign kept.
-__device__ __host__ inline uint32_t mx4_code(uint32_t u, int E) {
-  const uint32_t sign = (u >> 28) & 0x8u;
-  const uint32_t a = u & 0x7FFFFFFFu;
-  if (a >= 0x7F800000u) return sign | 0x7u;
-  if (a == 0u) return sign;
-  // |x| = M * 2^(ex - 23) with M in [2^23, 2^24)
-  uint32_t M = a & 0x007FFFFFu;
-  int ex = (int)(a >> 23) - 127;
-  if (a < 0x00800000u) {
-    const int lz = __builtin_clz(M) - 8;  // 1..23
-    M <<= lz;
-    ex = -126 - lz;
+// The one place where an mx cast code becomes compile-time tags: calls
+// f(format, bf16) with a format struct of mx_codec.h and whether the tensor
+// side is bf16 (else f32).
+template <typename F>
+__device__ __forceinline__ void mx_dispatch(uint32_t cast, F&& f) {
+  const bool fp4 = cast >= kCastF32toMX4;
+  if (mx_elem_size(cast) == 2) {
+    if (fp4) f(MxFp4E2M1{}, std::true_type{});
+    else f(MxFp8E4M3{}, std::true_type{});
   } else {
-    M |= 0x00800000u;
+    if (fp4) f(MxFp4E2M1{}, std::false_type{});
+    else f(MxFp8E4M3{}, std::false_type{});
   }
-  // y = |x| * 2^-E has exponent t. From t = 0 up it is an e2m1 normal with
-  // step 2^(t-1): q = RNE(M / 2^22) in [2, 4], and a carry to 4 runs into
-  // the exponent field. Below, the step stays 2^-1 (the one e2m1 subnormal).
-  const int t = ex - E;
-  const int shift = 22 + (t < 0 ? -t : 0);
-  const uint32_t sh = shift > 26 ? 26u : (uint32_t)shift;  // >= 25 gives 0
-  const uint32_t q = (M + ((1u << (sh - 1)) - 1u) + ((M >> sh) & 1u)) >> sh;
-  const uint32_t code = t >= 0 ? ((uint32_t)t << 1) + q : q;
-  return sign | (code > 0x7u ? 0x7u : code);
-}
-
-// f32 pattern of e2m1(code) * 2^(X - 127): exact, f32 subnormals included
-__device__ __host__ inline uint32_t mx4_decode_bits(uint32_t c, uint32_t X) {
-  const uint32_t sign = (c & 0x8u) << 28;
-  const uint32_t m = c & 0x7u;
-  if (X == 0xFFu) return sign | 0x7FC00000u;
-  if (m == 0u) return sign;
-  // 0.5 is the subnormal; from 1 on, 2^(ef-1) * (1 + mant / 2)
-  const int ex = m == 1u ? -1 : (int)(m >> 1) - 1;
-  const uint32_t frac = m == 1u ? 0u : (m & 1u) << 22;
-  const int biased = ex + (int)X;  // ex + (X - 127) + 127
-  if (biased >= 255) return sign | 0x7F800000u;
-  if (biased > 0) return sign | ((uint32_t)biased << 23) | frac;
-  // only the top two bits of the significand are set and the shift is at
-  // most 2: nothing is lost
-  return sign | ((0x00800000u | frac) >> (1 - biased));
-}
-
-// Aligned gather of [s, e) of the codes region of one work unit, 4 code bytes
-// per lane; the unit's scale bytes go to `lds`.
-template <bool BF16, bool HASH>
-__device__ unsigned long long mx4_gather_aligned(const Desc& d, char* flat_base,
-                                                 uint32_t s, uint32_t e,
-                                                 unsigned char* lds) {
-  char* flat = flat_base + d.flat_off;
-  unsigned long long h = 0;
-  for (uint32_t i = s + threadIdx.x * 4; i < e; i += kBlockThreads * 4) {
-    uint32_t valid;
-    const char* src = mx_aligned_addr<BF16 ? 2 : 4>(d, 2 * i, valid);
-    uint32_t v[8];
-    mx_load8<BF16>(src, valid, v);
-    uint32_t amax = 0;
-    bool nonfinite = false;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      amax = max(amax, mx_amax_of(v[k]));
-      nonfinite = nonfinite || (v[k] & 0x7FFFFFFFu) >= 0x7F800000u;
-    }
-    // e and the unit are whole blocks: the four lanes of a block are all
-    // here or all gone
-    amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
-    amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2, 64));
-    const bool block_nonfinite =
-        ((__ballot(nonfinite) >> (threadIdx.x & 60u)) & 0xFull) != 0;
-    const int E = mx4_block_exp(amax);
-    uint32_t o = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) o |= mx4_code(v[k], E) << (4 * k);
-    *reinterpret_cast<uint32_t*>(flat + i) = o;
-    if (HASH) h += psum_piece(o, d.flat_off + i);
-    if ((threadIdx.x & 3u) == 0u) {
-      lds[(i - s) >> 4] = block_nonfinite ? 0xFFu : (unsigned char)(E + 127);
-    }
-  }
-  return h;
-}
-
-// The general class's walk: the f32 pattern of the element at (p, col), then
-// one step on in row-major order; `more` is false at the tensor's last element
-template <bool BF16>
-__device__ __forceinline__ uint32_t mx_walk_load(const Desc& d, const char*& p,
-                                                 uint32_t& row, uint32_t& col,
-                                                 bool more) {
-  const char* q = p + (unsigned long long)(BF16 ? 2 : 4) * col;
-  const uint32_t u = BF16 ? (uint32_t)*reinterpret_cast<const uint16_t*>(q) << 16
-                          : *reinterpret_cast<const uint32_t*>(q);
-  if (++col == d.row_bytes && more) {
-    col = 0;
-    p = d.tensor_base + row_offset(d, ++row);
-  }
-  return u;
-}
-
-// General gather: one lane per block, walking rows twice.
-template <bool BF16, bool HASH>
-__device__ unsigned long long mx4_gather_general(const Desc& d, char* flat_base,
-                                                 uint32_t s, uint32_t e,
-                                                 unsigned char* lds) {
-  char* flat = flat_base + d.flat_off;
-  const uint32_t n = mx_numel(d);
-  unsigned long long h = 0;
-  for (uint32_t i0 = s + threadIdx.x * kMx4BlockBytes; i0 < e;
-       i0 += kBlockThreads * kMx4BlockBytes) {
-    // the block's first element exists: nbytes is ceil(n / 32) blocks
-    const uint32_t el0 = 2 * i0;
-    const uint32_t count = min(n - el0, kMxBlock);
-    const uint32_t row0 = el0 / d.row_bytes;
-    const uint32_t col0 = el0 - row0 * d.row_bytes;
-    const char* const p0 = d.tensor_base + row_offset(d, row0);
-
-    uint32_t row = row0, col = col0;
-    const char* p = p0;
-    uint32_t amax = 0;
-    bool nonfinite = false;
-    for (uint32_t j = 0; j < count; ++j) {
-      const uint32_t u = mx_walk_load<BF16>(d, p, row, col, j + 1 < count);
-      amax = max(amax, mx_amax_of(u));
-      nonfinite = nonfinite || (u & 0x7FFFFFFFu) >= 0x7F800000u;
-    }
-    const int E = mx4_block_exp(amax);
-
-    row = row0, col = col0, p = p0;
-    uint4 o = make_uint4(0u, 0u, 0u, 0u);
-    for (uint32_t j0 = 0; j0 < count; j0 += 8) {
-      uint32_t w = 0;
-#pragma unroll
-      for (uint32_t k = 0; k < 8; ++k) {
-        if (j0 + k < count) {
-          const uint32_t u =
-              mx_walk_load<BF16>(d, p, row, col, j0 + k + 1 < count);
-          w |= mx4_code(u, E) << (4 * k);
-        }
-      }
-      // selects, not an index: `o` stays in registers
-      if (j0 == 0) o.x = w;
-      else if (j0 == 8) o.y = w;
-      else if (j0 == 16) o.z = w;
-      else o.w = w;
-    }
-    *reinterpret_cast<uint4*>(flat + i0) = o;
-    if (HASH) h += psum_regs<16>(o, d.flat_off + i0);
-    lds[(i0 - s) >> 4] = nonfinite ? 0xFFu : (unsigned char)(E + 127);
-  }
-  return h;
-}
-
-// One mxfp4 descriptor's work unit of the gather: codes, then the scales.
-template <bool HASH>
-__device__ unsigned long long mx4_gather_unit(const Desc& d, char* flat_base,
-                                              uint32_t s, uint32_t e,
-                                              unsigned char* lds) {
-  const bool bf16 = d.cast == kCastBF16toMX4;
-  unsigned long long h;
-  if (d.vec == 8) {
-    h = bf16 ? mx4_gather_aligned<true, HASH>(d, flat_base, s, e, lds)
-             : mx4_gather_aligned<false, HASH>(d, flat_base, s, e, lds);
-  } else {
-    h = bf16 ? mx4_gather_general<true, HASH>(d, flat_base, s, e, lds)
-             : mx4_gather_general<false, HASH>(d, flat_base, s, e, lds);
-  }
-  const unsigned long long scales_off = d.flat_off + d.nbytes + (s >> 4);
-  return h + mx_move_scales<true, HASH>(flat_base + scales_off, lds,
-                                        (e - s) >> 4, scales_off);
 }
 
 // pack_kernel for batches that hold an mx descriptor; plain and cast
@@ -1185,31 +1064,19 @@ __global__ __launch_bounds__(kBlockThreads) void pack_mx_kernel(
     const unsigned long long* __restrict__ wu_prefix,
     unsigned long long total_wus, char* __restrict__ flat_base,
     unsigned long long* __restrict__ hash_out) {
-  __shared__ uint4 lds_scales[kMx4UnitBlocks / 16];
+  __shared__ uint4 lds_scales[kMxUnitBlocks / 16];
   unsigned char* lds = reinterpret_cast<unsigned char*>(lds_scales);
   for_each_work_unit(
       descs, n, wu_prefix, total_wus,
       [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
         unsigned long long h = 0;
-        if (is_mx4_cast(d.cast)) {
-          h = mx4_gather_unit<HASH>(d, flat_base, s, e, lds);
-        } else if (is_mx_cast(d.cast)) {
-          h = mx_gather_unit<HASH>(d, flat_base, s, e, lds);
-        } else if (d.cast != kCastNone) {
-          switch (d.vec) {
-            case 16: h = cast_range<16, HASH>(d, flat_base, s, e); break;
-            case 8: h = cast_range<8, HASH>(d, flat_base, s, e); break;
-            case 4: h = cast_range<4, HASH>(d, flat_base, s, e); break;
-            default: h = cast_range<2, HASH>(d, flat_base, s, e); break;
-          }
+        if (is_mx_cast(d.cast)) {
+          mx_dispatch(d.cast, [&](auto fmt, auto bf16) {
+            h = mx_gather_unit<decltype(fmt), decltype(bf16)::value, HASH>(
+                d, flat_base, s, e, lds);
+          });
         } else {
-          switch (d.vec) {
-            case 16: h = gather_range<16, HASH>(d, flat_base, s, e); break;
-            case 8: h = gather_range<8, HASH>(d, flat_base, s, e); break;
-            case 4: h = gather_range<4, HASH>(d, flat_base, s, e); break;
-            case 2: h = gather_range<2, HASH>(d, flat_base, s, e); break;
-            default: h = gather_range<1, HASH>(d, flat_base, s, e); break;
-          }
+          h = pack_unit<HASH, true>(d, flat_base, s, e);
         }
         if (HASH) add_per_wave(&hash_out[owner], h);
       });
@@ -1217,9 +1084,9 @@ __global__ __launch_bounds__(kBlockThreads) void pack_mx_kernel(
 
 // the decoded element as the target stores it: an f32 pattern, or its bf16
 // rounding (to nearest even) in the low half
-template <bool BF16>
+template <typename FMT, bool BF16>
 __device__ __forceinline__ uint32_t mx_out(uint32_t code, uint32_t X) {
-  const uint32_t f = mx_decode_bits(code, X);
+  const uint32_t f = mx_decode<FMT>(code, X);
   return BF16 ? (f32_to_bf16_bits(f) & 0xFFFFu) : f;
 }
 
@@ -1248,160 +1115,82 @@ __device__ __forceinline__ void mx_store8(char* dst, uint32_t valid,
   }
 }
 
+// code j of the dwords c[], element 0 lowest
+template <typename FMT>
+__device__ __forceinline__ uint32_t mx_code_at(const uint32_t* c, uint32_t j) {
+  constexpr uint32_t CPW = 32 / FMT::kBits;
+  return (c[j / CPW] >> (FMT::kBits * (j % CPW))) & ((1u << FMT::kBits) - 1u);
+}
+
 // Aligned scatter of [s, e) of the codes region; the unit's scales are in
 // `lds` already.
-template <bool BF16, bool HASH>
+template <typename FMT, bool BF16, bool HASH>
 __device__ unsigned long long mx_scatter_aligned(const Desc& d,
                                                  const char* flat_base,
                                                  uint32_t s, uint32_t e,
                                                  unsigned long long hash_off,
                                                  const unsigned char* lds) {
+  constexpr uint32_t LB = FMT::kBits;  // code bytes of 8 elements
   const char* flat = flat_base + d.flat_off;
   unsigned long long h = 0;
-  for (uint32_t i = s + threadIdx.x * 8; i < e; i += kBlockThreads * 8) {
-    const uint2 c = *reinterpret_cast<const uint2*>(flat + i);
-    if (HASH) {
-      h += (((unsigned long long)c.y << 32) | c.x) *
-           psum_mult((hash_off + i) >> 3);
-    }
-    const uint32_t X = lds[(i - s) >> 5];
+  for (uint32_t i = s + threadIdx.x * LB; i < e; i += kBlockThreads * LB) {
+    uint32_t c[2];
+    mx_load_lane<FMT, HASH>(flat + i, c, hash_off + i, h);
+    const uint32_t X = lds[(i - s) / FMT::kBlockBytes];
     uint32_t valid;
-    char* dst = const_cast<char*>(mx_aligned_addr<BF16 ? 2 : 4>(d, i, valid));
+    char* dst = const_cast<char*>(
+        mx_aligned_addr<BF16 ? 2 : 4>(d, i * (8 / LB), valid));
     uint32_t o[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      o[k] = mx_out<BF16>(((k < 4 ? c.x : c.y) >> (8 * (k & 3))) & 0xFFu, X);
+    for (uint32_t k = 0; k < 8; ++k) {
+      o[k] = mx_out<FMT, BF16>(mx_code_at<FMT>(c, k), X);
     }
     mx_store8<BF16>(dst, valid, o);
   }
   return h;
 }
 
-// General scatter: one lane per block, walking rows.
-template <bool BF16, bool HASH>
+// General scatter: one lane per block, walking rows once.
+template <typename FMT, bool BF16, bool HASH>
 __device__ unsigned long long mx_scatter_general(const Desc& d,
                                                  const char* flat_base,
                                                  uint32_t s, uint32_t e,
                                                  unsigned long long hash_off,
                                                  const unsigned char* lds) {
   constexpr int TS = BF16 ? 2 : 4;
+  constexpr uint32_t BB = FMT::kBlockBytes;
+  constexpr uint32_t CPW = 32 / FMT::kBits;  // codes per dword
   const char* flat = flat_base + d.flat_off;
   char* base = const_cast<char*>(d.tensor_base);
   const uint32_t rb = d.row_bytes;
   const uint32_t n = mx_numel(d);
   unsigned long long h = 0;
-  for (uint32_t i0 = s + threadIdx.x * kMxBlock; i0 < e;
-       i0 += kBlockThreads * kMxBlock) {
-    const uint4 a = *reinterpret_cast<const uint4*>(flat + i0);
-    const uint4 b = *reinterpret_cast<const uint4*>(flat + i0 + 16);
-    if (HASH) {
-      h += psum_regs<16>(a, hash_off + i0) + psum_regs<16>(b, hash_off + i0 + 16);
-    }
-    const uint32_t c[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    const uint32_t X = lds[(i0 - s) >> 5];
-    uint32_t row = i0 / rb;
-    uint32_t col = i0 - row * rb;
-    char* p = base + row_offset(d, row);
+  for (uint32_t i0 = s + threadIdx.x * BB; i0 < e; i0 += kBlockThreads * BB) {
+    uint32_t c[BB / 4];
 #pragma unroll
-    for (uint32_t j = 0; j < kMxBlock; ++j) {
-      if (i0 + j < n) {
-        const uint32_t o = mx_out<BF16>((c[j >> 2] >> (8 * (j & 3))) & 0xFFu, X);
-        char* q = p + (unsigned long long)TS * col;
-        if (BF16) *reinterpret_cast<uint16_t*>(q) = (uint16_t)o;
-        else *reinterpret_cast<uint32_t*>(q) = o;
-        if (++col == rb && i0 + j + 1 < n) {
-          col = 0;
-          p = base + row_offset(d, ++row);
-        }
-      }
+    for (uint32_t piece = 0; piece < BB / 16; ++piece) {
+      const uint4 a =
+          *reinterpret_cast<const uint4*>(flat + i0 + 16 * piece);
+      if (HASH) h += psum_regs<16>(a, hash_off + i0 + 16 * piece);
+      c[4 * piece] = a.x;
+      c[4 * piece + 1] = a.y;
+      c[4 * piece + 2] = a.z;
+      c[4 * piece + 3] = a.w;
     }
-  }
-  return h;
-}
-
-// One mx descriptor's work unit of the scatter: the scales, then the codes.
-template <bool HASH>
-__device__ unsigned long long mx_scatter_unit(const Desc& d,
-                                              const char* flat_base, uint32_t s,
-                                              uint32_t e,
-                                              unsigned long long hash_off,
-                                              unsigned char* lds) {
-  const unsigned long long scales_off =
-      (unsigned long long)d.nbytes + (s >> 5);
-  unsigned long long h = mx_move_scales<false, HASH>(
-      const_cast<char*>(flat_base) + d.flat_off + scales_off, lds, (e - s) >> 5,
-      hash_off + scales_off);
-  const bool bf16 = d.cast == kCastMXtoBF16;
-  if (d.vec == 8) {
-    h += bf16 ? mx_scatter_aligned<true, HASH>(d, flat_base, s, e, hash_off, lds)
-              : mx_scatter_aligned<false, HASH>(d, flat_base, s, e, hash_off, lds);
-  } else {
-    h += bf16 ? mx_scatter_general<true, HASH>(d, flat_base, s, e, hash_off, lds)
-              : mx_scatter_general<false, HASH>(d, flat_base, s, e, hash_off, lds);
-  }
-  return h;
-}
-
-// the decoded fp4 element as the target stores it; exact in bf16 as well, a
-// decoded value has at most two significant bits
-template <bool BF16>
-__device__ __forceinline__ uint32_t mx4_out(uint32_t code, uint32_t X) {
-  const uint32_t f = mx4_decode_bits(code, X);
-  return BF16 ? (f32_to_bf16_bits(f) & 0xFFFFu) : f;
-}
-
-// Aligned fp4 scatter of [s, e) of the codes region: 4 code bytes in, 8
-// elements out per lane; the unit's scales are in `lds` already.
-template <bool BF16, bool HASH>
-__device__ unsigned long long mx4_scatter_aligned(const Desc& d,
-                                                  const char* flat_base,
-                                                  uint32_t s, uint32_t e,
-                                                  unsigned long long hash_off,
-                                                  const unsigned char* lds) {
-  const char* flat = flat_base + d.flat_off;
-  unsigned long long h = 0;
-  for (uint32_t i = s + threadIdx.x * 4; i < e; i += kBlockThreads * 4) {
-    const uint32_t c = *reinterpret_cast<const uint32_t*>(flat + i);
-    if (HASH) h += psum_piece(c, hash_off + i);
-    const uint32_t X = lds[(i - s) >> 4];
-    uint32_t valid;
-    char* dst =
-        const_cast<char*>(mx_aligned_addr<BF16 ? 2 : 4>(d, 2 * i, valid));
-    uint32_t o[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) o[k] = mx4_out<BF16>((c >> (4 * k)) & 0xFu, X);
-    mx_store8<BF16>(dst, valid, o);
-  }
-  return h;
-}
-
-// General fp4 scatter: one lane per block, walking rows.
-template <bool BF16, bool HASH>
-__device__ unsigned long long mx4_scatter_general(const Desc& d,
-                                                  const char* flat_base,
-                                                  uint32_t s, uint32_t e,
-                                                  unsigned long long hash_off,
-                                                  const unsigned char* lds) {
-  constexpr int TS = BF16 ? 2 : 4;
-  const char* flat = flat_base + d.flat_off;
-  char* base = const_cast<char*>(d.tensor_base);
-  const uint32_t rb = d.row_bytes;
-  const uint32_t n = mx_numel(d);
-  unsigned long long h = 0;
-  for (uint32_t i0 = s + threadIdx.x * kMx4BlockBytes; i0 < e;
-       i0 += kBlockThreads * kMx4BlockBytes) {
-    const uint4 c = *reinterpret_cast<const uint4*>(flat + i0);
-    if (HASH) h += psum_regs<16>(c, hash_off + i0);
-    const uint32_t X = lds[(i0 - s) >> 4];
-    const uint32_t el0 = 2 * i0;
+    const uint32_t X = lds[(i0 - s) / BB];
+    const uint32_t el0 = i0 * (8 / FMT::kBits);
     const uint32_t count = min(n - el0, kMxBlock);
     uint32_t row = el0 / rb;
     uint32_t col = el0 - row * rb;
     char* p = base + row_offset(d, row);
     for (uint32_t j = 0; j < count; ++j) {
       // selects, not an index: `c` stays in registers
-      const uint32_t w = j < 8 ? c.x : j < 16 ? c.y : j < 24 ? c.z : c.w;
-      const uint32_t o = mx4_out<BF16>((w >> (4 * (j & 7u))) & 0xFu, X);
+      uint32_t w = c[0];
+#pragma unroll
+      for (uint32_t k = 1; k < BB / 4; ++k) {
+        if (j >= k * CPW) w = c[k];
+      }
+      const uint32_t o = mx_out<FMT, BF16>(mx_code_at<FMT>(&w, j % CPW), X);
       char* q = p + (unsigned long long)TS * col;
       if (BF16) *reinterpret_cast<uint16_t*>(q) = (uint16_t)o;
       else *reinterpret_cast<uint32_t*>(q) = o;
@@ -1414,27 +1203,22 @@ __device__ unsigned long long mx4_scatter_general(const Desc& d,
   return h;
 }
 
-// One mxfp4 descriptor's work unit of the scatter: the scales, then the codes.
-template <bool HASH>
-__device__ unsigned long long mx4_scatter_unit(const Desc& d,
-                                               const char* flat_base,
-                                               uint32_t s, uint32_t e,
-                                               unsigned long long hash_off,
-                                               unsigned char* lds) {
+// One mx descriptor's work unit of the scatter: the scales, then the codes.
+template <typename FMT, bool BF16, bool HASH>
+__device__ unsigned long long mx_scatter_unit(const Desc& d,
+                                              const char* flat_base, uint32_t s,
+                                              uint32_t e,
+                                              unsigned long long hash_off,
+                                              unsigned char* lds) {
   const unsigned long long scales_off =
-      (unsigned long long)d.nbytes + (s >> 4);
-  unsigned long long h = mx_move_scales<false, HASH>(
-      const_cast<char*>(flat_base) + d.flat_off + scales_off, lds, (e - s) >> 4,
-      hash_off + scales_off);
-  const bool bf16 = d.cast == kCastMX4toBF16;
-  if (d.vec == 8) {
-    h += bf16 ? mx4_scatter_aligned<true, HASH>(d, flat_base, s, e, hash_off, lds)
-              : mx4_scatter_aligned<false, HASH>(d, flat_base, s, e, hash_off, lds);
-  } else {
-    h += bf16 ? mx4_scatter_general<true, HASH>(d, flat_base, s, e, hash_off, lds)
-              : mx4_scatter_general<false, HASH>(d, flat_base, s, e, hash_off, lds);
-  }
-  return h;
+      (unsigned long long)d.nbytes + s / FMT::kBlockBytes;
+  const unsigned long long h = mx_move_scales<false, HASH>(
+      const_cast<char*>(flat_base) + d.flat_off + scales_off, lds,
+      (e - s) / FMT::kBlockBytes, hash_off + scales_off);
+  return h + (d.vec == 8 ? mx_scatter_aligned<FMT, BF16, HASH>(
+                               d, flat_base, s, e, hash_off, lds)
+                         : mx_scatter_general<FMT, BF16, HASH>(
+                               d, flat_base, s, e, hash_off, lds));
 }
 
 // unpack_kernel for batches that hold an mx descriptor
@@ -1445,33 +1229,20 @@ __global__ __launch_bounds__(kBlockThreads) void unpack_mx_kernel(
     unsigned long long total_wus, const char* __restrict__ flat_base,
     unsigned long long* __restrict__ hash_out,
     unsigned long long hash_byte0) {
-  __shared__ uint4 lds_scales[kMx4UnitBlocks / 16];
+  __shared__ uint4 lds_scales[kMxUnitBlocks / 16];
   unsigned char* lds = reinterpret_cast<unsigned char*>(lds_scales);
   for_each_work_unit(
       descs, n, wu_prefix, total_wus,
       [&](int owner, const Desc& d, uint32_t s, uint32_t e) {
         const unsigned long long ho = hash_byte0 + d.flat_off;
-        const char* fb = flat_base;
         unsigned long long h = 0;
-        if (is_mx4_cast(d.cast)) {
-          h = mx4_scatter_unit<HASH>(d, fb, s, e, ho, lds);
-        } else if (is_mx_cast(d.cast)) {
-          h = mx_scatter_unit<HASH>(d, fb, s, e, ho, lds);
-        } else if (d.cast != kCastNone) {
-          switch (d.vec) {
-            case 16: h = widen_range<16, HASH>(d, fb, s, e, ho); break;
-            case 8: h = widen_range<8, HASH>(d, fb, s, e, ho); break;
-            case 4: h = widen_range<4, HASH>(d, fb, s, e, ho); break;
-            default: h = widen_range<2, HASH>(d, fb, s, e, ho); break;
-          }
+        if (is_mx_cast(d.cast)) {
+          mx_dispatch(d.cast, [&](auto fmt, auto bf16) {
+            h = mx_scatter_unit<decltype(fmt), decltype(bf16)::value, HASH>(
+                d, flat_base, s, e, ho, lds);
+          });
         } else {
-          switch (d.vec) {
-            case 16: h = scatter_range<16, HASH>(d, fb, s, e, ho); break;
-            case 8: h = scatter_range<8, HASH>(d, fb, s, e, ho); break;
-            case 4: h = scatter_range<4, HASH>(d, fb, s, e, ho); break;
-            case 2: h = scatter_range<2, HASH>(d, fb, s, e, ho); break;
-            default: h = scatter_range<1, HASH>(d, fb, s, e, ho); break;
-          }
+          h = unpack_unit<HASH, true>(d, flat_base, s, e, ho);
         }
         if (HASH) add_per_wave(&hash_out[owner], h);
       });
